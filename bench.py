@@ -9,8 +9,15 @@ C3 shoots 4e7 packets per wavelength (1e9 in all) on 8 GPUs, so a step is one ra
 5e6 packets per wavelength, 1.25e8 packets. Weak scaling: every rank shoots its own slice of the global packet index space and, for N > 1, the
 phase ends with the reference's reductions (Labs all-reduce, instrument all-reduce) done by RCCL.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--full] [--dump-outputs DIR]
        (N > 1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
+       A plain run sets up, warms up, times the K steps and prints the line (the roofline fields come from
+       the timed steps' own counters). --full adds what takes runs of its own: the CPU baseline (the oracle
+       on the host's cores, about 20 s; --no-cpu-baseline leaves it out again).
+       --dump-outputs DIR writes the tallies the last timed step left in the caller's bound tensors as
+       DIR/labs.npy, DIR/instruments.npy (and DIR/dust_labs.npy for C5), float64, flattened as the engine
+       lays them out, at most DUMP_BUDGET_BYTES in all: an array over its share is cut down to a fixed
+       seeded sample of its elements (dump_sample), the same in every run of the same arguments.
        --dist-backend gloo runs the same sharded path over gloo (ranks may then share one GPU: rank r uses
        device LOCAL_RANK mod the visible device count), to rehearse N > 1 on a one-GPU box;
        --digest adds the summed tallies (Labs per wavelength, instrument totals) to the line, so that an
@@ -121,6 +128,35 @@ def cpu_baseline(ski, target_seconds=20.0):
         per, nl, per * nl, r.packets, r.seconds)
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # --dump-outputs: all files together, headers included, stay below 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_sample(n, keep):
+    """The sorted indices of the `keep` of `n` elements that --dump-outputs writes of an array over its share:
+    a function of (n, keep) alone."""
+    import numpy as np
+
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+
+
+def dump_outputs(outdir, arrays):
+    """Writes {name: flat float64 array} as outdir/<name>.npy within DUMP_BUDGET_BYTES: the arrays are served
+    smallest first, each with an equal share of what is left, so that small ones go whole."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    order = sorted(arrays, key=lambda k: arrays[k].size)
+    for i, name in enumerate(order):
+        a = np.ascontiguousarray(arrays[name], dtype=np.float64).reshape(-1)
+        keep = min(a.size, (left // (len(order) - i) - 128) // 8)  # 128: the .npy header
+        if keep < a.size:
+            a = a[dump_sample(a.size, keep)]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes + 128
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -128,7 +164,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--packets-per-lambda", type=int, default=0, help="per rank; default per config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baseline (the oracle on the host's cores)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's tallies as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--threshold", type=int, default=0, help="idle lanes before a wave pulls rays (0 = engine default)")
     ap.add_argument("--slots", type=int, default=0, help="packet slots in flight (0 = engine default)")
     ap.add_argument("--trace-grid", type=int, default=0, help="trace kernel workgroups (0 = occupancy-derived)")
@@ -136,6 +176,8 @@ def main():
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI)")
     ap.add_argument("--digest", action="store_true", help="report the reduced tallies' sums")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -356,7 +398,14 @@ def main():
                                   "labs_total": float(labs_l.sum()),
                                   "sed_total": float(seds.sum()) if seds is not None else None,
                                   "frame_total": float(frames.sum()) if frames is not None else None}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs and rank == 0:
+        # what a caller of step() holds after the last timed step: the bound tally tensors (summed over the
+        # ranks by the engine's reducer)
+        out = {"labs": labs, "instruments": instr}
+        if dust_phases:
+            out["dust_labs"] = dust
+        dump_outputs(args.dump_outputs, {k: t.cpu().numpy() for k, t in out.items()})
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         v, cores, sample = cpu_baseline(ski)
         result["cpu_baseline"] = {"value": v, "unit": "photon packets/s", "cores": cores, "kind": "port",
                                   "sample": sample}

@@ -13,7 +13,8 @@ import oracle_lib as O
 import tree_models as T
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_DAT = "/root/reference/dat/DustMix"
+# the reference's data files dat/DustMix/{MeanZubkoDustMix,DraineLiDustMix}.dat, stored as fixtures
+REF_DAT = os.path.join(REPO, "tests", "golden", "dustmix")
 
 
 def read_bin(name):
@@ -22,7 +23,6 @@ def read_bin(name):
         return np.frombuffer(f.read(), dtype="<f8").reshape(nrows, ncols)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DAT), reason="reference data files absent (GPU box)")
 @pytest.mark.parametrize("name,n", [("MeanZubkoDustMix", 1201), ("DraineLiDustMix", 800)])
 def test_packaged_tables_hold_the_reference_numbers(name, n):
     rows = []

@@ -36,7 +36,7 @@ case $preset in
 round)
   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" &&
   TAILN=3 run pytest_gpu 1200 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread &&
-  run bench_default 600 python bench.py &&
+  run bench_default 600 python bench.py --full &&
   run bench_c2 300 python bench.py --config c2 --steps 3 --warmup 1 --no-cpu-baseline &&
   run bench_c4 300 python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline &&
   run bench_c5 300 python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline &&
