@@ -49,7 +49,7 @@ enum {
                                   ds_crossed bin; the message names the limit and the sizes */
 };
 
-enum { SKIRT_GRID_CARTESIAN = 0, SKIRT_GRID_OCTREE = 1, SKIRT_GRID_VORONOI = 2 };
+enum { SKIRT_GRID_CARTESIAN = 0, SKIRT_GRID_OCTREE = 1, SKIRT_GRID_VORONOI = 2, SKIRT_GRID_CYLINDER2D = 3 };
 enum { SKIRT_TREE_TOPDOWN = 0, SKIRT_TREE_NEIGHBOR = 1, SKIRT_TREE_BOOKKEEPING = 2 /* octrees only */ };
 enum { SKIRT_GEOM_PLUMMER = 0, SKIRT_GEOM_EXPDISK = 1, SKIRT_GEOM_SERSIC = 2, SKIRT_GEOM_POINT = 3 };
 enum { SKIRT_INSTR_FULL = 0, SKIRT_INSTR_SIMPLE = 1, SKIRT_INSTR_SED = 2, SKIRT_INSTR_FRAME = 3 };
@@ -63,7 +63,10 @@ typedef struct SkirtMcrt SkirtMcrt;
  * breadth-first node vector (TreeDustGrid.cpp:50-164): per node a box {xmin,ymin,zmin,xmax,ymax,zmax},
  * the index of its first of 8 consecutive children (-1 for a leaf) and its cell number (-1 for
  * non-leaves); neighbor lists per (node, wall) in CSR form, walls BACK FRONT LEFT RIGHT BOTTOM TOP,
- * each list sorted by decreasing overlap (TreeNode::sortneighbors). */
+ * each list sorted by decreasing overlap (TreeNode::sortneighbors). Cylinder2D (Cylinder2DDustGrid.cpp, an
+ * axisymmetric R-z grid): nx = N_R with xv the N_R+1 radial borders (xv[0] = 0), nz = N_z with zv the N_z+1
+ * z borders, ny = 0 and yv unused, ncells = N_R*N_z, cell index m = k + nz*i (Cylinder2DDustGrid::index);
+ * eps unused. */
 typedef struct {
     int kind;
     int ncells;
@@ -197,7 +200,7 @@ typedef struct {
 
 /* grid walks of the trace kernel (SkirtStats::grid_walk) */
 enum { SKIRT_WALK_CARTESIAN = 0, SKIRT_WALK_OCTREE_MAP = 1, SKIRT_WALK_VORONOI = 2, SKIRT_WALK_TREE_NODES = 3,
-       SKIRT_WALK_KDTREE_MAP = 4, SKIRT_WALK_OCTREE_BOOKKEEPING = 5 };
+       SKIRT_WALK_KDTREE_MAP = 4, SKIRT_WALK_OCTREE_BOOKKEEPING = 5, SKIRT_WALK_CYLINDER2D = 6 };
 
 int skirt_mcrt_abi_version(void);
 int skirt_mcrt_create(int device, SkirtMcrt** out);

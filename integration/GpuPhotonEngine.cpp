@@ -9,6 +9,7 @@
 #include "ArrayTable.hpp"
 #include "Box.hpp"
 #include "CartesianDustGrid.hpp"
+#include "Cylinder2DDustGrid.hpp"
 #include "DistantInstrument.hpp"
 #include "DustMix.hpp"
 #include "DustSystem.hpp"
@@ -192,6 +193,24 @@ void GpuPhotonEngine::describeGrid()
         g.nz = borders(cg->meshZ(), cg->minZ(), cg->maxZ(), zv);
         g.xv = xv.data();
         g.yv = yv.data();
+        g.zv = zv.data();
+    }
+    else if (Cylinder2DDustGrid* yg = dynamic_cast<Cylinder2DDustGrid*>(grid))
+    {
+        // the borders as Cylinder2DDustGrid::setupSelfAfter computes them (Cylinder2DDustGrid.cpp:26-32): the
+        // radial ones in xv (nx = N_R), the vertical ones in zv (nz = N_z), ny = 0
+        Array tR = yg->meshR()->mesh();
+        Array tz = yg->meshZ()->mesh();
+        const double Rmax = yg->maxR(), zmin = yg->minZ(), zmax = yg->maxZ();
+        xv.resize(tR.size());
+        zv.resize(tz.size());
+        for (size_t i = 0; i < tR.size(); i++) xv[i] = tR[i] * Rmax;
+        for (size_t k = 0; k < tz.size(); k++) zv[k] = tz[k] * (zmax - zmin) + zmin;
+        g.kind = SKIRT_GRID_CYLINDER2D;
+        g.nx = yg->meshR()->numBins();
+        g.ny = 0;
+        g.nz = yg->meshZ()->numBins();
+        g.xv = xv.data();
         g.zv = zv.data();
     }
     else if (TreeDustGrid* tg = dynamic_cast<TreeDustGrid*>(grid))

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "vor_terms.hpp"
+#include "cyl2d_walk.hpp"
 #include "../../../include/skirt_mcrt.h"
 #include "philox.hpp"
 
@@ -457,7 +458,8 @@ __device__ __forceinline__ Shared stageTables(const Args& a, double* lds, int pa
 
 template <int GRID>
 __device__ __forceinline__ constexpr int gridParts() {
-    return GRID == SKIRT_GRID_CARTESIAN ? STAGE_MESH : ((GRID == SKIRT_GRID_OCTREE || GRID == kBinTreeMap) ? STAGE_TREE : 0);
+    return (GRID == SKIRT_GRID_CARTESIAN || GRID == SKIRT_GRID_CYLINDER2D) ? STAGE_MESH
+           : ((GRID == SKIRT_GRID_OCTREE || GRID == kBinTreeMap) ? STAGE_TREE : 0);
 }
 
 // The counters live in kStatCopies copies of one 64-byte line each (summed by the host): the waves of a
@@ -488,10 +490,13 @@ struct Ray {
     double kext;           // kappa_ext at the ray's wavelength (one dust component)
     double param;          // see RayRec::param
     double f1, f2;         // FILL: exp(-tau), Lsca | WALK: tau and s at the previous segment end
-    double bx0, by0, bz0, bx1, by1, bz1;  // octree walked through the node arrays: box of the node
+    double bx0, by0, bz0, bx1, by1, bz1;  // octree walked through the node arrays: box of the node |
+                                          //   cylindrical walk: q, p, k_q, k_z, q_N (Grid<SKIRT_GRID_CYLINDER2D>)
     double rho0;           // density (component 0) of the current cell
-    int ci, cj, ck;        // Cartesian cell indices | octree: node, cell number, leaf size in finest cells
-    int jx, jy, jz;        // octree leaf map: finest-level index of the current leaf's lower corner
+    int ci, cj, ck;        // Cartesian cell indices | octree: node, cell number, leaf size in finest cells |
+                           //   cylindrical walk: i, i_min, k
+    int jx, jy, jz;        // octree leaf map: finest-level index of the current leaf's lower corner |
+                           //   cylindrical walk: jx = 1 while the ray moves inward
     int4 pre;              // octree leaf map: the next step's leaf-map entry, requested at the end of this step
     int pfx, pfy, pfz;     //   and the finest-level cell it was requested for (LeafMapGrid::prefetch)
     double ex, ey, ez, eds;  // octree leaf map: the current leaf's exit point and distance, and its wall,
@@ -629,6 +634,57 @@ struct Grid<SKIRT_GRID_CARTESIAN> {
         const int i = locateFail(xv, a.nx + 1, x), j = locateFail(yv, a.ny + 1, y), k = locateFail(zv, a.nz + 1, z);
         if (i < 0 || j < 0 || k < 0) return -1;
         return dev(a, i, j, k);
+    }
+};
+
+// Axisymmetric R-z grid: Cylinder2DDustGrid.cpp:135-362 through device/cyl2d_walk.hpp (the walk's arithmetic,
+// shared with the CPU logic test). The borders R | (one unused word, ny = 0) | z are staged in LDS like the
+// Cartesian mesh; device cell number = reference cell number k + nz i, so the cells of one radial shell that
+// are adjacent in z share Labs lines. The walk's state lives in registers the Cartesian walk leaves unused:
+// q, p, k_q, k_z, q_N in bx0, by0, bz0, bx1, by1; z in r.z; i, i_min, k in ci, cj, ck; inward in jx.
+template <>
+struct Grid<SKIRT_GRID_CYLINDER2D> {
+    __device__ static __forceinline__ const double* zBorders(const Args& a, const Shared& sh) {
+        return sh.mesh + a.nx + 1 + a.ny + 1;
+    }
+    __device__ static __forceinline__ Cyl2dState get(const Ray& r) {
+        return Cyl2dState{r.bx0, r.z, r.by0, r.bz0, r.bx1, r.by1, r.ci, r.ck, r.cj, r.jx};
+    }
+    __device__ static __forceinline__ void put(Ray& r, const Cyl2dState& s) {
+        r.bx0 = s.q; r.z = s.z; r.by0 = s.p; r.bz0 = s.kq; r.bx1 = s.kz; r.by1 = s.qN;
+        r.ci = s.i; r.ck = s.k; r.cj = s.imin; r.jx = s.inward;
+    }
+    __device__ static __forceinline__ int dev(const Args& a, int i, int k) { return k + a.nz * i; }
+
+    // the entry part of the path: the segments outside the grid (m = -1), then the first cell; false for an
+    // empty path
+    template <class SegFn>
+    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
+        Cyl2dState s;
+        if (!cyl2dEnter(sh.mesh, a.nx, zBorders(a, sh), a.nz, r.x, r.y, r.z, r.dx, r.dy, r.dz, s,
+                        [&](int m, double ds) { seg(m, 0.0, ds); }))
+            return false;
+        put(r, s);
+        r.rho0 = a.rho[(size_t)dev(a, s.i, s.k) * a.ncomp];
+        return true;
+    }
+
+    // one grid step: emits (m, ds); false when the ray ends (left the grid or stopped by seg)
+    template <class SegFn>
+    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
+        Cyl2dState s = get(r);
+        const double rho0 = r.rho0;  // loaded by the previous step (or begin), off this step's chain
+        int m;
+        double ds;
+        const bool more = cyl2dStep(sh.mesh, a.nx, zBorders(a, sh), a.nz, s, m, ds);
+        if (!seg(m, rho0, ds) || !more) return false;
+        put(r, s);
+        r.rho0 = a.rho[(size_t)dev(a, s.i, s.k) * a.ncomp];  // the next step's density, requested now
+        return true;
+    }
+
+    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
+        return cyl2dWhichCell(sh.mesh, a.nx, zBorders(a, sh), a.nz, x, y, z);
     }
 };
 
@@ -2446,17 +2502,29 @@ struct Events {
             m = locateGuided(cdf, guide, N, X);
         }
         if (GRID == SKIRT_GRID_VORONOI) m = a.devCell[m];  // the Voronoi arrays are in device order
-        double b[6];
-        cellBox(m, b);
-        // VoronoiMesh::randomPosition: points in the enclosing box until one lies in the cell
-        for (int trial = 0; trial < (GRID == SKIRT_GRID_VORONOI ? 10000 : 1); trial++) {
-            const double x = p.rng.uniform();
-            const double y = p.rng.uniform();
-            const double z = p.rng.uniform();
-            p.rx = b[0] + x * (b[3] - b[0]);
-            p.ry = b[1] + y * (b[4] - b[1]);
-            p.rz = b[2] + z * (b[5] - b[2]);
-            if (GRID != SKIRT_GRID_VORONOI || Grid<SKIRT_GRID_VORONOI>::closestTo(a, p.rx, p.ry, p.rz, m)) break;
+        if constexpr (GRID == SKIRT_GRID_CYLINDER2D) {
+            // Cylinder2DDustGrid::randomPositionInCell: three deviates in the order R, phi, z
+            const double* Rv = sh.mesh;
+            const double* zv = Grid<SKIRT_GRID_CYLINDER2D>::zBorders(a, sh);
+            const int i = m / a.nz, k = m % a.nz;
+            const double R = Rv[i] + (Rv[i + 1] - Rv[i]) * p.rng.uniform();
+            const double phi = 2.0 * M_PI * p.rng.uniform();
+            p.rz = zv[k] + (zv[k + 1] - zv[k]) * p.rng.uniform();
+            p.rx = R * cos(phi);
+            p.ry = R * sin(phi);
+        } else {
+            double b[6];
+            cellBox(m, b);
+            // VoronoiMesh::randomPosition: points in the enclosing box until one lies in the cell
+            for (int trial = 0; trial < (GRID == SKIRT_GRID_VORONOI ? 10000 : 1); trial++) {
+                const double x = p.rng.uniform();
+                const double y = p.rng.uniform();
+                const double z = p.rng.uniform();
+                p.rx = b[0] + x * (b[3] - b[0]);
+                p.ry = b[1] + y * (b[4] - b[1]);
+                p.rz = b[2] + z * (b[5] - b[2]);
+                if (GRID != SKIRT_GRID_VORONOI || Grid<SKIRT_GRID_VORONOI>::closestTo(a, p.rx, p.ry, p.rz, m)) break;
+            }
         }
         isotropic(p.rng, p.kx, p.ky, p.kz);
         p.L = L;
@@ -3805,6 +3873,24 @@ int skirt_mcrt_upload_grid(SkirtMcrt* c, const SkirtGridDesc* g) {
         if ((rc = upload(c, c->dBlockOffset, g->block_offset, nb3 + 1))) return rc;
         if ((rc = upload(c, c->dBlockSites, blocks.data(), blocks.size()))) return rc;
         if ((rc = upload(c, c->dDevCell, c->devCell.data(), c->devCell.size()))) return rc;
+    } else if (g->kind == SKIRT_GRID_CYLINDER2D) {
+        if (g->nx < 1 || g->nz < 1 || !g->xv || !g->zv) return fail(c, SKIRT_ERR_ARG, "bad cylindrical grid");
+        if ((long long)g->nx * g->nz != g->ncells) return fail(c, SKIRT_ERR_ARG, "ncells != nx*nz");
+        if (g->xv[0] != 0.0) return fail(c, SKIRT_ERR_ARG, "the radial mesh does not start at 0");
+        for (int i = 0; i < g->nx; i++) if (!(g->xv[i] < g->xv[i + 1])) return fail(c, SKIRT_ERR_ARG, "R mesh not increasing");
+        for (int i = 0; i < g->nz; i++) if (!(g->zv[i] < g->zv[i + 1])) return fail(c, SKIRT_ERR_ARG, "z mesh not increasing");
+        // R | one unused word | z: the Cartesian mesh layout with ny = 0
+        std::vector<double> mesh;
+        mesh.insert(mesh.end(), g->xv, g->xv + g->nx + 1);
+        mesh.push_back(0.0);
+        mesh.insert(mesh.end(), g->zv, g->zv + g->nz + 1);
+        c->nx = g->nx; c->ny = 0; c->nz = g->nz;
+        c->gx0 = -g->xv[g->nx]; c->gx1 = g->xv[g->nx];
+        c->gy0 = -g->xv[g->nx]; c->gy1 = g->xv[g->nx];
+        c->gz0 = g->zv[0]; c->gz1 = g->zv[g->nz];
+        c->mapL = -1;
+        int rc = upload(c, c->dMesh, mesh.data(), mesh.size());
+        if (rc) return rc;
     } else {
         return fail(c, SKIRT_ERR_UNSUPPORTED, "unsupported grid kind");
     }
@@ -4410,7 +4496,8 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
     // LDS layout (doubles): mesh | optics | instruments | SED sums
     int off = 0;
     a.ldsMeshOff = off;
-    off += (c->gridKind == SKIRT_GRID_CARTESIAN && a.hasDust) ? (c->nx + c->ny + c->nz + 3) : 0;
+    const bool meshGrid = c->gridKind == SKIRT_GRID_CARTESIAN || c->gridKind == SKIRT_GRID_CYLINDER2D;
+    off += (meshGrid && a.hasDust) ? (c->nx + c->ny + c->nz + 3) : 0;
     off += leafMap ? 3 * (c->mapN + 1) : 0;
     off = (off + 1) & ~1;
     a.ldsOptOff = off;
@@ -4448,6 +4535,7 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
                                         (int)ldsDetect));
     const int kind = c->gridKind == SKIRT_GRID_CARTESIAN ? SKIRT_GRID_CARTESIAN
                      : c->gridKind == SKIRT_GRID_VORONOI ? SKIRT_GRID_VORONOI
+                     : c->gridKind == SKIRT_GRID_CYLINDER2D ? SKIRT_GRID_CYLINDER2D
                      : bookkeeping ? kOctreeBookkeeping
                      : (leafMap ? (c->binTree ? kBinTreeMap : SKIRT_GRID_OCTREE) : kOctreeNodes);
     c->lastWalk = kind == SKIRT_GRID_CARTESIAN ? SKIRT_WALK_CARTESIAN
@@ -4455,6 +4543,7 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
                   : kind == kBinTreeMap        ? SKIRT_WALK_KDTREE_MAP
                   : kind == kOctreeBookkeeping ? SKIRT_WALK_OCTREE_BOOKKEEPING
                   : kind == SKIRT_GRID_VORONOI ? SKIRT_WALK_VORONOI
+                  : kind == SKIRT_GRID_CYLINDER2D ? SKIRT_WALK_CYLINDER2D
                                                : SKIRT_WALK_TREE_NODES;
     const bool one = a.ncomp == 1;
     const void* traceFn = nullptr;
@@ -4469,6 +4558,7 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
     else if (kind == SKIRT_GRID_OCTREE) SKIRT_PICK(SKIRT_GRID_OCTREE);
     else if (kind == kBinTreeMap) SKIRT_PICK(kBinTreeMap);
     else if (kind == kOctreeBookkeeping) SKIRT_PICK(kOctreeBookkeeping);
+    else if (kind == SKIRT_GRID_CYLINDER2D) SKIRT_PICK(SKIRT_GRID_CYLINDER2D);
     else if (kind == SKIRT_GRID_VORONOI) {
         if (a.labsGlobal)
             pick(traceKernelVor<true, false, true>, traceKernelVor<false, false, true>, traceKernelVor<true, true, true>,
@@ -4513,6 +4603,7 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
         else if (kind == SKIRT_GRID_OCTREE) { if (one) SKIRT_EVENT(SKIRT_GRID_OCTREE, true); else SKIRT_EVENT(SKIRT_GRID_OCTREE, false); }
         else if (kind == kBinTreeMap) { if (one) SKIRT_EVENT(kBinTreeMap, true); else SKIRT_EVENT(kBinTreeMap, false); }
         else if (kind == kOctreeBookkeeping) { if (one) SKIRT_EVENT(kOctreeBookkeeping, true); else SKIRT_EVENT(kOctreeBookkeeping, false); }
+        else if (kind == SKIRT_GRID_CYLINDER2D) { if (one) SKIRT_EVENT(SKIRT_GRID_CYLINDER2D, true); else SKIRT_EVENT(SKIRT_GRID_CYLINDER2D, false); }
         else if (kind == SKIRT_GRID_VORONOI) { if (one) SKIRT_EVENT(SKIRT_GRID_VORONOI, true); else SKIRT_EVENT(SKIRT_GRID_VORONOI, false); }
         else { if (one) SKIRT_EVENT(kOctreeNodes, true); else SKIRT_EVENT(kOctreeNodes, false); }
 #undef SKIRT_EVENT
@@ -4523,6 +4614,7 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
         else if (kind == SKIRT_GRID_OCTREE) { if (one) SKIRT_CONT(SKIRT_GRID_OCTREE, true); else SKIRT_CONT(SKIRT_GRID_OCTREE, false); }
         else if (kind == kBinTreeMap) { if (one) SKIRT_CONT(kBinTreeMap, true); else SKIRT_CONT(kBinTreeMap, false); }
         else if (kind == kOctreeBookkeeping) { if (one) SKIRT_CONT(kOctreeBookkeeping, true); else SKIRT_CONT(kOctreeBookkeeping, false); }
+        else if (kind == SKIRT_GRID_CYLINDER2D) { if (one) SKIRT_CONT(SKIRT_GRID_CYLINDER2D, true); else SKIRT_CONT(SKIRT_GRID_CYLINDER2D, false); }
         else if (kind == SKIRT_GRID_VORONOI) { if (one) SKIRT_CONT(SKIRT_GRID_VORONOI, true); else SKIRT_CONT(SKIRT_GRID_VORONOI, false); }
         else { if (one) SKIRT_CONT(kOctreeNodes, true); else SKIRT_CONT(kOctreeNodes, false); }
 #undef SKIRT_CONT
@@ -4788,6 +4880,9 @@ int skirt_mcrt_column_densities(SkirtMcrt* c, const double* rays, int n, double*
     if (e == hipSuccess) {
         if (c->gridKind == SKIRT_GRID_CARTESIAN)
             hipLaunchKernelGGL(columnKernel<SKIRT_GRID_CARTESIAN>, grid, dim3(kBlock),
+                               (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
+        else if (c->gridKind == SKIRT_GRID_CYLINDER2D)
+            hipLaunchKernelGGL(columnKernel<SKIRT_GRID_CYLINDER2D>, grid, dim3(kBlock),
                                (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
         else if (c->gridKind == SKIRT_GRID_VORONOI)
             hipLaunchKernelGGL(columnKernel<SKIRT_GRID_VORONOI>, grid, dim3(kBlock), 0, c->stream, a, d, n, d + 6 * (size_t)n);

@@ -358,6 +358,7 @@ double WavelengthGrid::lambdamax(int ell) const {
 }
 
 void DustGrid::cellBox(int m, double b[6]) const {
+    if (kind == GridKind::Cylinder2D) throw std::runtime_error("a cylindrical dust cell has no Cartesian box");
     if (kind == GridKind::Voronoi) {
         for (int q = 0; q < 6; q++) b[q] = vor.bbox[6 * (size_t)m + q];
         return;
@@ -378,6 +379,12 @@ void DustGrid::cellCenter(int m, double c[3]) const {
         for (int q = 0; q < 3; q++) c[q] = vor.centroid[3 * (size_t)m + q];
         return;
     }
+    if (kind == GridKind::Cylinder2D) {  // Cylinder2DDustGrid::centralPositionInCell: (R, phi = 0, z)
+        const int i = m / cyl.Nz, k = m % cyl.Nz;
+        const double R = (cyl.Rv[i] + cyl.Rv[i + 1]) / 2.0, phi = 0.0;
+        c[0] = R * std::cos(phi); c[1] = R * std::sin(phi); c[2] = (cyl.zv[k] + cyl.zv[k + 1]) / 2.0;
+        return;
+    }
     double b[6];
     cellBox(m, b);
     for (int q = 0; q < 3; q++) c[q] = 0.5 * (b[q] + b[3 + q]);
@@ -385,6 +392,10 @@ void DustGrid::cellCenter(int m, double c[3]) const {
 
 double DustGrid::cellVolume(int m) const {
     if (kind == GridKind::Voronoi) return vor.volume[m];
+    if (kind == GridKind::Cylinder2D) {  // Cylinder2DDustGrid::volume
+        const int i = m / cyl.Nz, k = m % cyl.Nz;
+        return M_PI * (cyl.zv[k + 1] - cyl.zv[k]) * (cyl.Rv[i + 1] - cyl.Rv[i]) * (cyl.Rv[i + 1] + cyl.Rv[i]);
+    }
     double b[6];
     cellBox(m, b);
     return (b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]);
@@ -392,6 +403,11 @@ double DustGrid::cellVolume(int m) const {
 
 int DustGrid::whichcell(double x, double y, double z) const {
     if (kind == GridKind::Voronoi) return vor.cellIndex(x, y, z);
+    if (kind == GridKind::Cylinder2D) {  // Cylinder2DDustGrid::whichcell (Position::cylradius, height)
+        int i = nr::locateFail(cyl.Rv, std::sqrt(x * x + y * y)), k = nr::locateFail(cyl.zv, z);
+        if (i < 0 || k < 0) return -1;
+        return k + cyl.Nz * i;
+    }
     if (kind == GridKind::Cartesian) {
         int i = nr::locateFail(cart.xv, x), j = nr::locateFail(cart.yv, y), k = nr::locateFail(cart.zv, z);
         if (i < 0 || j < 0 || k < 0) return -1;
@@ -1348,6 +1364,71 @@ static void buildVoronoiGrid(const Ctx& c, const XmlElement* ge, Model& m, Unifo
     buildVoronoi(m.grid.vor, sites, xmin, xmax, ymin, ymax, zmin, zmax, c.sampler ? c.sampler->voronoiCells() : nullptr);
 }
 
+// A Mesh on [0,1] (LinMesh.cpp, PowMesh.cpp, SymPowMesh.cpp, LogMesh.cpp; NR::lingrid, NR::powgrid,
+// NR::sympowgrid, NR::zerologgrid, Fundamentals/NR.hpp:171-289): its N+1 borders. LogMesh is an AnchoredMesh,
+// not a MoveableMesh, so only a property of type Mesh accepts it.
+static std::vector<double> unitMesh(const Ctx& c, const XmlElement* me, int& N, bool allowLog) {
+    N = attrInt(me, "numBins", 100);
+    if (N < 1) throw std::runtime_error("the number of mesh bins should be positive");
+    std::vector<double> tv(N + 1);
+    auto lingrid = [&](int n) {
+        const double dx = (1.0 - 0.0) / n;
+        for (int i = 0; i <= n; i++) tv[i] = 0.0 + i * dx;
+    };
+    if (me->name == "LinMesh") {
+        lingrid(N);
+    } else if (me->name == "PowMesh" || me->name == "SymPowMesh") {
+        const double ratio = attr(c, me, "ratio", "", 1.0);
+        if (!(ratio > 0)) throw std::runtime_error("the bin width ratio should be positive");
+        const bool sym = me->name == "SymPowMesh";
+        if (sym ? N <= 2 : N <= 1) lingrid(N);
+        else if (std::fabs(ratio - 1.) < 1e-3) lingrid(N);
+        else if (!sym) {
+            const double range = 1.0 - 0.0;
+            const double q = std::pow(ratio, 1. / (N - 1));
+            const double qn = std::pow(q, N);
+            for (int i = 0; i <= N; ++i) tv[i] = 0.0 + (1. - std::pow(q, i)) / (1. - qn) * range;
+        } else {
+            const double xc = 0.5 * (0.0 + 1.0);
+            if (N % 2 == 0) {
+                const int M = N / 2;
+                const double q = std::pow(ratio, 1.0 / (M - 1.0));
+                const double qM = std::pow(q, M);
+                tv[M] = xc;
+                for (int i = 1; i <= M; ++i) {
+                    const double dxi = (1.0 - std::pow(q, i)) / (1.0 - qM) * 0.5 * (1.0 - 0.0);
+                    tv[M + i] = xc + dxi;
+                    tv[M - i] = xc - dxi;
+                }
+            } else {
+                const int M = (N + 1) / 2;
+                const double q = std::pow(ratio, 1.0 / (M - 1.0));
+                const double qM = std::pow(q, M);
+                for (int i = 1; i <= M; ++i) {
+                    const double dxi = (0.5 + 0.5 * q - std::pow(q, i)) / (0.5 + 0.5 * q - qM) * 0.5 * (1.0 - 0.0);
+                    tv[M - 1 + i] = xc + dxi;
+                    tv[M - i] = xc - dxi;
+                }
+            }
+        }
+    } else if (me->name == "LogMesh" && allowLog) {
+        // LogMesh::mesh (LogMesh.cpp): NR::zerologgrid(tv, tc, 1, N), or NR::lingrid for a single bin
+        const double tc = attr(c, me, "centralBinFraction", "", 0.0);
+        if (tc <= 0 || tc >= 1) throw std::runtime_error("The central bin width fraction should be within range ]0,1[");
+        if (N > 1) {
+            const double logxmin = std::log10(tc);
+            const double dlogx = std::log10(1.0 / tc) / (N - 1);
+            tv[0] = 0.0;
+            for (int i = 0; i < N; i++) tv[i + 1] = std::pow(10, logxmin + i * dlogx);
+        } else {
+            lingrid(N);
+        }
+    } else {
+        throw std::runtime_error("unsupported mesh " + me->name);
+    }
+    return tv;
+}
+
 Model loadSki(const std::string& path, UniformSource& rng, const std::string& datadir, DensitySampler* sampler) {
     auto doc = parseXmlFile(path);
     if (doc->children.empty()) throw std::runtime_error("empty ski file");
@@ -1481,53 +1562,7 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
             // NR::powgrid, NR::sympowgrid, Fundamentals/NR.hpp:171-261), then
             // _xv = mesh*(xmax-xmin) + xmin (CartesianDustGrid.cpp:34-36)
             auto mesh = [&](const char* prop, int& N, std::vector<double>& v, double lo, double hi) {
-                const XmlElement* me = need(ge, prop);
-                N = attrInt(me, "numBins", 100);
-                if (N < 1) throw std::runtime_error("the number of mesh bins should be positive");
-                std::vector<double> tv(N + 1);
-                auto lingrid = [&](int n) {
-                    const double dx = (1.0 - 0.0) / n;
-                    for (int i = 0; i <= n; i++) tv[i] = 0.0 + i * dx;
-                };
-                if (me->name == "LinMesh") {
-                    lingrid(N);
-                } else if (me->name == "PowMesh" || me->name == "SymPowMesh") {
-                    const double ratio = attr(c, me, "ratio", "", 1.0);
-                    if (!(ratio > 0)) throw std::runtime_error("the bin width ratio should be positive");
-                    const bool sym = me->name == "SymPowMesh";
-                    if (sym ? N <= 2 : N <= 1) lingrid(N);
-                    else if (std::fabs(ratio - 1.) < 1e-3) lingrid(N);
-                    else if (!sym) {
-                        const double range = 1.0 - 0.0;
-                        const double q = std::pow(ratio, 1. / (N - 1));
-                        const double qn = std::pow(q, N);
-                        for (int i = 0; i <= N; ++i) tv[i] = 0.0 + (1. - std::pow(q, i)) / (1. - qn) * range;
-                    } else {
-                        const double xc = 0.5 * (0.0 + 1.0);
-                        if (N % 2 == 0) {
-                            const int M = N / 2;
-                            const double q = std::pow(ratio, 1.0 / (M - 1.0));
-                            const double qM = std::pow(q, M);
-                            tv[M] = xc;
-                            for (int i = 1; i <= M; ++i) {
-                                const double dxi = (1.0 - std::pow(q, i)) / (1.0 - qM) * 0.5 * (1.0 - 0.0);
-                                tv[M + i] = xc + dxi;
-                                tv[M - i] = xc - dxi;
-                            }
-                        } else {
-                            const int M = (N + 1) / 2;
-                            const double q = std::pow(ratio, 1.0 / (M - 1.0));
-                            const double qM = std::pow(q, M);
-                            for (int i = 1; i <= M; ++i) {
-                                const double dxi = (0.5 + 0.5 * q - std::pow(q, i)) / (0.5 + 0.5 * q - qM) * 0.5 * (1.0 - 0.0);
-                                tv[M - 1 + i] = xc + dxi;
-                                tv[M - i] = xc - dxi;
-                            }
-                        }
-                    }
-                } else {
-                    throw std::runtime_error("unsupported mesh " + me->name);
-                }
+                const std::vector<double> tv = unitMesh(c, need(ge, prop), N, false);
                 v.resize(N + 1);
                 for (int i = 0; i <= N; i++) v[i] = tv[i] * (hi - lo) + lo;
             };
@@ -1545,6 +1580,22 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
             StageTimer st("voronoi");
             buildVoronoiGrid(c, ge, m, rng);
             m.grid.ncells = m.grid.vor.ncells();
+        } else if (ge->name == "Cylinder2DDustGrid") {
+            // CylinderDustGrid::setupSelfBefore, Cylinder2DDustGrid::setupSelfAfter
+            m.grid.kind = GridKind::Cylinder2D;
+            Cylinder2DGrid& g = m.grid.cyl;
+            g.Rmax = attr(c, ge, "maxR", "length", 0);
+            g.zmin = attr(c, ge, "minZ", "length", 0);
+            g.zmax = attr(c, ge, "maxZ", "length", 0);
+            if (g.Rmax <= 0) throw std::runtime_error("The outer radius of the grid should be positive");
+            if (g.zmax <= g.zmin) throw std::runtime_error("The extent of the Cylinder should be positive in the Z direction");
+            const std::vector<double> tR = unitMesh(c, need(ge, "meshR"), g.NR, true);
+            const std::vector<double> tz = unitMesh(c, need(ge, "meshZ"), g.Nz, false);
+            g.Rv.resize(g.NR + 1);
+            g.zv.resize(g.Nz + 1);
+            for (int i = 0; i <= g.NR; i++) g.Rv[i] = tR[i] * g.Rmax;
+            for (int k = 0; k <= g.Nz; k++) g.zv[k] = tz[k] * (g.zmax - g.zmin) + g.zmin;
+            m.grid.ncells = g.NR * g.Nz;
         } else {
             throw std::runtime_error("unsupported dust grid " + ge->name);
         }
@@ -1627,6 +1678,22 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
                     });
                 for (auto& x : th) x.join();
             }
+        } else if (m.grid.kind == GridKind::Cylinder2D) {
+            // Cylinder2DDustGrid::randomPositionInCell per sample: three deviates (R, phi, z), drawn ahead in
+            // cell order; always on the host (the device sampler draws in boxes)
+            const Cylinder2DGrid& g = m.grid.cyl;
+            parallelDraws(rng, (size_t)Ncells, 3 * m.sampleCount, [&](size_t cell, const double* u) {
+                const int i = (int)cell / g.Nz, k = (int)cell % g.Nz;
+                std::vector<double> sumv(Ncomp, 0.0);
+                for (int n = 0; n < m.sampleCount; n++) {
+                    const double R = g.Rv[i] + (g.Rv[i + 1] - g.Rv[i]) * u[3 * n];
+                    const double phi = 2.0 * M_PI * u[3 * n + 1];
+                    const double z = g.zv[k] + (g.zv[k + 1] - g.zv[k]) * u[3 * n + 2];
+                    const double x = R * std::cos(phi), y = R * std::sin(phi);
+                    for (int h = 0; h < Ncomp; h++) sumv[h] += m.dust[h].density(x, y, z);
+                }
+                for (int h = 0; h < Ncomp; h++) m.rho[cell * Ncomp + h] = 1.0 * sumv[h] / m.sampleCount;
+            });
         } else {
             // Random::position(box) per sample: three deviates, drawn ahead in cell order
             const bool onDevice = deviceSampling(

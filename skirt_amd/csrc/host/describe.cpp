@@ -36,6 +36,11 @@ void writeGrid(Writer& w, const SkirtGridDesc& g) {
         w.d("grid.xv", g.xv, (size_t)g.nx + 1);
         w.d("grid.yv", g.yv, (size_t)g.ny + 1);
         w.d("grid.zv", g.zv, (size_t)g.nz + 1);
+    } else if (g.kind == SKIRT_GRID_CYLINDER2D) {
+        w.i1("grid.nx", g.nx);
+        w.i1("grid.nz", g.nz);
+        w.d("grid.xv", g.xv, (size_t)g.nx + 1);
+        w.d("grid.zv", g.zv, (size_t)g.nz + 1);
     } else if (g.kind == SKIRT_GRID_OCTREE) {
         const size_t n = (size_t)g.nnodes;
         w.i1("grid.nnodes", g.nnodes);

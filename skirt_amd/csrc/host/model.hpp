@@ -152,17 +152,27 @@ struct OctreeGrid {
     }
 };
 
-enum class GridKind : int { Cartesian = 0, Octree = 1, Voronoi = 2 };
+// Axisymmetric R-z grid: SKIRTcore/Cylinder2DDustGrid.cpp (CylinderDustGrid.cpp); cell m = k + Nz*i
+struct Cylinder2DGrid {
+    int NR = 0, Nz = 0;
+    double Rmax = 0, zmin = 0, zmax = 0;
+    std::vector<double> Rv, zv;  // NR+1 radial borders (Rv[0] = 0), Nz+1 z borders
+};
+
+enum class GridKind : int { Cartesian = 0, Octree = 1, Voronoi = 2, Cylinder2D = 3 };
 
 struct DustGrid {
     GridKind kind = GridKind::Cartesian;
     CartesianGrid cart;
     OctreeGrid tree;
     VoronoiGrid vor;
+    Cylinder2DGrid cyl;
     int ncells = 0;
-    void cellBox(int m, double b[6]) const;  // xmin ymin zmin xmax ymax zmax (Voronoi: the enclosing box)
+    // xmin ymin zmin xmax ymax zmax (Voronoi: the enclosing box; not defined for a cylindrical grid)
+    void cellBox(int m, double b[6]) const;
     double cellVolume(int m) const;
-    // DustGrid::centralPositionInCell: the box centre, or the centroid of a Voronoi cell
+    // DustGrid::centralPositionInCell: the box centre, the centroid of a Voronoi cell, or (R, phi = 0, z) at the
+    // middle of a cylindrical cell's borders
     void cellCenter(int m, double c[3]) const;
     int whichcell(double x, double y, double z) const;
 };

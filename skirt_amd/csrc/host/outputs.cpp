@@ -298,6 +298,7 @@ void writeOutputs(const Model& m, const std::string& prefix, const std::vector<s
         f.column("optical depth");
         double totalmass = 0;
         for (auto& d : m.dust) totalmass += d.nf;
+        std::vector<double> tauV(Ncells);
         for (int c = 0; c < Ncells; c++) {
             double rho = 0;
             for (int h = 0; h < Ncomp; h++) rho += m.rho[(size_t)c * Ncomp + h];
@@ -305,6 +306,31 @@ void writeOutputs(const Model& m, const std::string& prefix, const std::vector<s
             double delta = (rho * V) / totalmass;
             double tau = constants::kappaV * rho * std::pow(V, 1. / 3.);
             f.row({units.ovolume(V), units.omassvolumedensity(rho), delta, tau});
+            tauV[c] = tau;
+        }
+        // The statistics lines that close the reference's file (DustSystem.cpp:663-687), for the cylindrical
+        // grid, whose file then equals the reference's byte for byte. The files of the grid kinds that came
+        // before it keep their form (rows only).
+        if (m.grid.kind == GridKind::Cylinder2D && Ncells > 0) {
+            double tausum = 0;
+            for (double t : tauV) tausum += t;
+            const double tauavg = tausum / Ncells;
+            const double taumin = *std::min_element(tauV.begin(), tauV.end());
+            const double taumax = *std::max_element(tauV.begin(), tauV.end());
+            const int Nbins = 500;
+            std::vector<int> countV(Nbins + 1);
+            for (int c = 0; c < Ncells; c++)
+                countV[std::max(0, std::min(Nbins, static_cast<int>((tauV[c] - taumin) / (taumax - taumin) * Nbins)))]++;
+            int count = 0, index = 0;
+            for (; index < Nbins; index++) {
+                count += countV[index];
+                if (count > 0.9 * Ncells) break;
+            }
+            const double tau90 = taumin + index * (taumax - taumin) / Nbins;
+            f.line("# smallest optical depth: " + qtNumber(taumin, 'g', 6));
+            f.line("# largest optical depth:  " + qtNumber(taumax, 'g', 6));
+            f.line("# average optical depth:  " + qtNumber(tauavg, 'g', 6));
+            f.line("# 90 % of the cells have optical depth smaller than: " + qtNumber(tau90, 'g', 6));
         }
     }
 }

@@ -191,7 +191,8 @@ int skirt_sim_info(SkirtSim* s, SkirtSimInfo* o) {
     o->ncomp = s->m.ncomp();
     o->ninstruments = (int)s->m.instruments.size();
     o->grid_kind = s->m.grid.kind == GridKind::Octree ? SKIRT_GRID_OCTREE
-                   : s->m.grid.kind == GridKind::Voronoi ? SKIRT_GRID_VORONOI : SKIRT_GRID_CARTESIAN;
+                   : s->m.grid.kind == GridKind::Voronoi ? SKIRT_GRID_VORONOI
+                   : s->m.grid.kind == GridKind::Cylinder2D ? SKIRT_GRID_CYLINDER2D : SKIRT_GRID_CARTESIAN;
     o->nnodes = s->m.grid.kind == GridKind::Octree ? s->m.grid.tree.nnodes() : 0;
     o->npp = s->npp;
     o->total_packets = s->npp * (uint64_t)s->m.wl.n();
@@ -245,6 +246,10 @@ void buildDescs(const Model& m, Descs& d) {
             g.kind = SKIRT_GRID_CARTESIAN;
             g.nx = m.grid.cart.Nx; g.ny = m.grid.cart.Ny; g.nz = m.grid.cart.Nz;
             g.xv = m.grid.cart.xv.data(); g.yv = m.grid.cart.yv.data(); g.zv = m.grid.cart.zv.data();
+        } else if (m.grid.kind == GridKind::Cylinder2D) {
+            g.kind = SKIRT_GRID_CYLINDER2D;
+            g.nx = m.grid.cyl.NR; g.ny = 0; g.nz = m.grid.cyl.Nz;
+            g.xv = m.grid.cyl.Rv.data(); g.zv = m.grid.cyl.zv.data();
         } else {
             const OctreeGrid& t = m.grid.tree;
             g.kind = SKIRT_GRID_OCTREE;
