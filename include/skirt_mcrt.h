@@ -49,7 +49,8 @@ enum {
                                   ds_crossed bin; the message names the limit and the sizes */
 };
 
-enum { SKIRT_GRID_CARTESIAN = 0, SKIRT_GRID_OCTREE = 1, SKIRT_GRID_VORONOI = 2, SKIRT_GRID_CYLINDER2D = 3 };
+enum { SKIRT_GRID_CARTESIAN = 0, SKIRT_GRID_OCTREE = 1, SKIRT_GRID_VORONOI = 2, SKIRT_GRID_CYLINDER2D = 3,
+       SKIRT_GRID_SPHERE1D = 4, SKIRT_GRID_SPHERE2D = 5 };
 enum { SKIRT_TREE_TOPDOWN = 0, SKIRT_TREE_NEIGHBOR = 1, SKIRT_TREE_BOOKKEEPING = 2 /* octrees only */ };
 enum { SKIRT_GEOM_PLUMMER = 0, SKIRT_GEOM_EXPDISK = 1, SKIRT_GEOM_SERSIC = 2, SKIRT_GEOM_POINT = 3 };
 enum { SKIRT_INSTR_FULL = 0, SKIRT_INSTR_SIMPLE = 1, SKIRT_INSTR_SED = 2, SKIRT_INSTR_FRAME = 3 };
@@ -66,7 +67,14 @@ typedef struct SkirtMcrt SkirtMcrt;
  * each list sorted by decreasing overlap (TreeNode::sortneighbors). Cylinder2D (Cylinder2DDustGrid.cpp, an
  * axisymmetric R-z grid): nx = N_R with xv the N_R+1 radial borders (xv[0] = 0), nz = N_z with zv the N_z+1
  * z borders, ny = 0 and yv unused, ncells = N_R*N_z, cell index m = k + nz*i (Cylinder2DDustGrid::index);
- * eps unused. */
+ * eps unused. Sphere1D and Sphere2D (Sphere1DDustGrid.cpp, Sphere2DDustGrid.cpp): nx = N_r with xv the N_r+1
+ * radial borders (meshR()->mesh()*maxR()); extent the bounding box -maxR() .. maxR(), so that extent[3] is
+ * maxR() exactly (the reference's routines test against it, and a LogMesh's last border may differ from it in
+ * the last bit). Sphere1D: ny = nz = 0, yv and zv unused, ncells = N_r, cell index m = i, eps unused. Sphere2D:
+ * nz = N_theta after Sphere2DDustGrid::setupSelfAfter (a border pi/2 inserted where the mesh has none) with zv
+ * the N_theta+1 polar borders theta, ny = N_theta with yv their N_theta+1 cosines after the same routine's
+ * fix-ups (exact 1, 0, -1), eps = 1e-11*maxR(), ncells = N_r*N_theta, cell index m = k + N_theta*i
+ * (Sphere2DDustGrid::index). */
 typedef struct {
     int kind;
     int ncells;
@@ -200,7 +208,8 @@ typedef struct {
 
 /* grid walks of the trace kernel (SkirtStats::grid_walk) */
 enum { SKIRT_WALK_CARTESIAN = 0, SKIRT_WALK_OCTREE_MAP = 1, SKIRT_WALK_VORONOI = 2, SKIRT_WALK_TREE_NODES = 3,
-       SKIRT_WALK_KDTREE_MAP = 4, SKIRT_WALK_OCTREE_BOOKKEEPING = 5, SKIRT_WALK_CYLINDER2D = 6 };
+       SKIRT_WALK_KDTREE_MAP = 4, SKIRT_WALK_OCTREE_BOOKKEEPING = 5, SKIRT_WALK_CYLINDER2D = 6,
+       SKIRT_WALK_SPHERE1D = 7, SKIRT_WALK_SPHERE2D = 8 };
 
 int skirt_mcrt_abi_version(void);
 int skirt_mcrt_create(int device, SkirtMcrt** out);

@@ -28,6 +28,8 @@
 #include "SersicFunction.hpp"
 #include "SersicGeometry.hpp"
 #include "SimpleInstrument.hpp"
+#include "Sphere1DDustGrid.hpp"
+#include "Sphere2DDustGrid.hpp"
 #include "StellarSystem.hpp"
 #include "TreeDustGrid.hpp"
 #include "TreeNode.hpp"
@@ -212,6 +214,71 @@ void GpuPhotonEngine::describeGrid()
         g.nz = yg->meshZ()->numBins();
         g.xv = xv.data();
         g.zv = zv.data();
+    }
+    else if (Sphere1DDustGrid* s1 = dynamic_cast<Sphere1DDustGrid*>(grid))
+    {
+        // the shells as Sphere1DDustGrid::setupSelfAfter computes them (Sphere1DDustGrid.cpp:30-32) in xv; the
+        // extent carries maxR(), which path() and whichcell() test against
+        Array tr = s1->meshR()->mesh();
+        const double rmax = s1->maxR();
+        xv.resize(tr.size());
+        for (size_t i = 0; i < tr.size(); i++) xv[i] = tr[i] * rmax;
+        g.kind = SKIRT_GRID_SPHERE1D;
+        g.nx = s1->meshR()->numBins();
+        g.ny = 0;
+        g.nz = 0;
+        g.xv = xv.data();
+        for (int q = 0; q < 3; q++) { g.extent[q] = -rmax; g.extent[3 + q] = rmax; }
+    }
+    else if (Sphere2DDustGrid* s2 = dynamic_cast<Sphere2DDustGrid*>(grid))
+    {
+        // Sphere2DDustGrid::setupSelfAfter (Sphere2DDustGrid.cpp:33-82) restated: the shells in xv, the polar
+        // borders in zv and their cosines in yv, with exact cosines at the poles, a cosine within 1e-9 of zero
+        // made zero, and a border at pi/2 inserted where the mesh has none (the grid checked for two such points)
+        Array tr = s2->meshR()->mesh();
+        Array tt = s2->meshTheta()->mesh();
+        const double rmax = s2->maxR();
+        xv.resize(tr.size());
+        for (size_t i = 0; i < tr.size(); i++) xv[i] = tr[i] * rmax;
+        int Ntheta = s2->meshTheta()->numBins();
+        std::vector<double> thetav(Ntheta + 1), cv(Ntheta + 1);
+        for (int k = 0; k <= Ntheta; k++) thetav[k] = tt[k] * M_PI;
+        for (int k = 0; k <= Ntheta; k++) cv[k] = cos(thetav[k]);
+        cv[0] = 1.;
+        cv[Ntheta] = -1.;
+        int numzeroes = 0;
+        for (int k = 1; k < Ntheta; k++)
+        {
+            if (fabs(cv[k]) < 1e-9)
+            {
+                numzeroes++;
+                cv[k] = 0.;
+            }
+        }
+        if (numzeroes == 0)
+        {
+            const std::vector<double> orTheta = thetav, orC = cv;
+            Ntheta++;
+            thetav.assign(Ntheta + 1, M_PI_2);
+            cv.assign(Ntheta + 1, 0.);
+            for (int k = 0; k < Ntheta; k++)
+            {
+                const int target = (orC[k] > 0) ? k : k + 1;
+                thetav[target] = orTheta[k];
+                cv[target] = orC[k];
+            }
+        }
+        yv = cv;
+        zv = thetav;
+        g.kind = SKIRT_GRID_SPHERE2D;
+        g.nx = s2->meshR()->numBins();
+        g.ny = Ntheta;
+        g.nz = Ntheta;
+        g.xv = xv.data();
+        g.yv = yv.data();
+        g.zv = zv.data();
+        g.eps = 1e-11 * rmax;
+        for (int q = 0; q < 3; q++) { g.extent[q] = -rmax; g.extent[3 + q] = rmax; }
     }
     else if (TreeDustGrid* tg = dynamic_cast<TreeDustGrid*>(grid))
     {

@@ -24,7 +24,7 @@ ABI_VERSION = 14  # SKIRT_MCRT_ABI_VERSION of include/skirt_mcrt.h
 LIB_PATH = os.path.join(PKG_DIR, os.environ.get("SKIRT_AMD_LIB", "libskirt_amd.so"))
 DATA_DIR = os.path.join(PKG_DIR, "data")
 
-GRID_CARTESIAN, GRID_OCTREE, GRID_VORONOI, GRID_CYLINDER2D = 0, 1, 2, 3
+GRID_CARTESIAN, GRID_OCTREE, GRID_VORONOI, GRID_CYLINDER2D, GRID_SPHERE1D, GRID_SPHERE2D = 0, 1, 2, 3, 4, 5
 # SkirtStats.grid_walk: the trace kernel's grid walk in the last run (SKIRT_WALK_*)
 WALK_CARTESIAN, WALK_OCTREE_MAP, WALK_VORONOI, WALK_TREE_NODES, WALK_KDTREE_MAP, WALK_OCTREE_BOOKKEEPING = 0, 1, 2, 3, 4, 5
 
@@ -153,7 +153,8 @@ class Simulation:
         """setup_device: a HIP device for the setup's density sampling (tree subdivision, cell densities);
         None keeps the setup on the host, bit-identical to the reference. A Cylinder2DDustGrid (info.grid_kind ==
         GRID_CYLINDER2D) samples its cell densities on the host either way: the device sampler draws positions in
-        boxes, a cylindrical cell draws (R, phi, z)."""
+        boxes, a cylindrical cell draws (R, phi, z). The same holds for a Sphere1DDustGrid and a Sphere2DDustGrid
+        (GRID_SPHERE1D, GRID_SPHERE2D), whose cells draw (direction, r) and (r, theta, phi)."""
         L = lib()
         self._h = L.skirt_sim_load_ex(os.fspath(ski).encode(), (datadir or DATA_DIR).encode(), float(packages),
                                       int(seed), -1 if setup_device is None else int(setup_device))

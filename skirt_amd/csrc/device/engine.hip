@@ -34,6 +34,7 @@
 
 #include "vor_terms.hpp"
 #include "cyl2d_walk.hpp"
+#include "sph_walk.hpp"
 #include "../../../include/skirt_mcrt.h"
 #include "philox.hpp"
 
@@ -458,7 +459,8 @@ __device__ __forceinline__ Shared stageTables(const Args& a, double* lds, int pa
 
 template <int GRID>
 __device__ __forceinline__ constexpr int gridParts() {
-    return (GRID == SKIRT_GRID_CARTESIAN || GRID == SKIRT_GRID_CYLINDER2D) ? STAGE_MESH
+    return (GRID == SKIRT_GRID_CARTESIAN || GRID == SKIRT_GRID_CYLINDER2D || GRID == SKIRT_GRID_SPHERE1D ||
+            GRID == SKIRT_GRID_SPHERE2D) ? STAGE_MESH
            : ((GRID == SKIRT_GRID_OCTREE || GRID == kBinTreeMap) ? STAGE_TREE : 0);
 }
 
@@ -491,12 +493,14 @@ struct Ray {
     double param;          // see RayRec::param
     double f1, f2;         // FILL: exp(-tau), Lsca | WALK: tau and s at the previous segment end
     double bx0, by0, bz0, bx1, by1, bz1;  // octree walked through the node arrays: box of the node |
-                                          //   cylindrical walk: q, p, k_q, k_z, q_N (Grid<SKIRT_GRID_CYLINDER2D>)
+                                          //   cylindrical walk: q, p, k_q, k_z, q_N (Grid<SKIRT_GRID_CYLINDER2D>) |
+                                          //   Sphere1D walk: q, p, q_N (Grid<SKIRT_GRID_SPHERE1D>)
     double rho0;           // density (component 0) of the current cell
     int ci, cj, ck;        // Cartesian cell indices | octree: node, cell number, leaf size in finest cells |
-                           //   cylindrical walk: i, i_min, k
+                           //   cylindrical walk: i, i_min, k | Sphere1D walk: i, i_min |
+                           //   Sphere2D walk: i, steps left, k (the position advances in x, y, z)
     int jx, jy, jz;        // octree leaf map: finest-level index of the current leaf's lower corner |
-                           //   cylindrical walk: jx = 1 while the ray moves inward
+                           //   cylindrical and Sphere1D walks: jx = 1 while the ray moves inward
     int4 pre;              // octree leaf map: the next step's leaf-map entry, requested at the end of this step
     int pfx, pfy, pfz;     //   and the finest-level cell it was requested for (LeafMapGrid::prefetch)
     double ex, ey, ez, eds;  // octree leaf map: the current leaf's exit point and distance, and its wall,
@@ -685,6 +689,94 @@ struct Grid<SKIRT_GRID_CYLINDER2D> {
 
     __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
         return cyl2dWhichCell(sh.mesh, a.nx, zBorders(a, sh), a.nz, x, y, z);
+    }
+};
+
+// Spherical shells: Sphere1DDustGrid.cpp:111-187 through device/sph_walk.hpp. The borders r (then two unused
+// words, ny = nz = 0) are staged in LDS like the Cartesian mesh; r_max = maxR() travels in gx1 (a LogMesh's last
+// border may miss it by a bit); device cell number = shell number. State: q, p, q_N in bx0, by0, bz0; i, i_min in
+// ci, cj; inward in jx. i moves monotonically in each part of the walk, so a path has at most 2 N_r steps.
+template <>
+struct Grid<SKIRT_GRID_SPHERE1D> {
+    __device__ static __forceinline__ Sph1dState get(const Ray& r) {
+        return Sph1dState{r.bx0, r.by0, r.bz0, r.ci, r.cj, r.jx};
+    }
+    __device__ static __forceinline__ void put(Ray& r, const Sph1dState& s) {
+        r.bx0 = s.q; r.by0 = s.p; r.bz0 = s.qN; r.ci = s.i; r.cj = s.imin; r.jx = s.inward;
+    }
+    __device__ static __forceinline__ int dev(const Args&, int i) { return i; }
+
+    template <class SegFn>
+    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
+        Sph1dState s;
+        if (!sph1dEnter(sh.mesh, a.nx, a.gx1, r.x, r.y, r.z, r.dx, r.dy, r.dz, s,
+                        [&](int m, double ds) { seg(m, 0.0, ds); }))
+            return false;
+        put(r, s);
+        r.rho0 = a.rho[(size_t)s.i * a.ncomp];
+        return true;
+    }
+
+    template <class SegFn>
+    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
+        Sph1dState s = get(r);
+        const double rho0 = r.rho0;  // loaded by the previous step (or begin), off this step's chain
+        int m;
+        double ds;
+        const bool more = sph1dStep(sh.mesh, a.nx, s, m, ds);
+        if (!seg(m, rho0, ds) || !more) return false;
+        put(r, s);
+        r.rho0 = a.rho[(size_t)s.i * a.ncomp];  // the next step's density, requested now
+        return true;
+    }
+
+    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
+        return sph1dWhichCell(sh.mesh, a.nx, x, y, z);
+    }
+};
+
+// Shells x polar bins: Sphere2DDustGrid.cpp:186-359 through device/sph_walk.hpp. The borders r | cos theta | theta
+// (nx = N_r, ny = nz = N_theta) are staged in LDS in the mesh layout; r_max in gx1, eps = 1e-11 r_max in a.eps;
+// device cell number = reference cell number k + N_theta i. The position advances in r.x, r.y, r.z; i, k in ci,
+// ck; the steps the path may still take (sph2dStepCap) in cj. A step that finds no exit nudges the position and
+// emits no segment (m = -1, ds = 0).
+template <>
+struct Grid<SKIRT_GRID_SPHERE2D> {
+    __device__ static __forceinline__ const double* cosBorders(const Args& a, const Shared& sh) {
+        return sh.mesh + a.nx + 1;
+    }
+    __device__ static __forceinline__ const double* thetaBorders(const Args& a, const Shared& sh) {
+        return sh.mesh + a.nx + 1 + a.ny + 1;
+    }
+    __device__ static __forceinline__ int dev(const Args& a, int i, int k) { return k + a.nz * i; }
+
+    template <class SegFn>
+    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
+        Sph2dState s;
+        if (!sph2dEnter(sh.mesh, a.nx, thetaBorders(a, sh), a.nz, a.gx1, a.eps, r.x, r.y, r.z, r.dx, r.dy, r.dz, s,
+                        [&](int m, double ds) { seg(m, 0.0, ds); }))
+            return false;
+        r.x = s.x; r.y = s.y; r.z = s.z; r.ci = s.i; r.ck = s.k; r.cj = s.left;
+        r.rho0 = a.rho[(size_t)dev(a, s.i, s.k) * a.ncomp];
+        return true;
+    }
+
+    template <class SegFn>
+    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
+        Sph2dState s{r.x, r.y, r.z, r.ci, r.ck, r.cj};
+        const double rho0 = r.rho0;  // loaded by the previous step (or begin), off this step's chain
+        int m;
+        double ds;
+        const bool more = sph2dStep(sh.mesh, a.nx, cosBorders(a, sh), thetaBorders(a, sh), a.nz, a.eps, r.dx, r.dy,
+                                    r.dz, s, m, ds);
+        if (!seg(m, rho0, ds) || !more) return false;
+        r.x = s.x; r.y = s.y; r.z = s.z; r.ci = s.i; r.ck = s.k; r.cj = s.left;
+        r.rho0 = a.rho[(size_t)dev(a, s.i, s.k) * a.ncomp];  // the next step's density, requested now
+        return true;
+    }
+
+    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
+        return sph2dWhichCell(sh.mesh, a.nx, thetaBorders(a, sh), a.nz, x, y, z);
     }
 };
 
@@ -2512,6 +2604,27 @@ struct Events {
             p.rz = zv[k] + (zv[k + 1] - zv[k]) * p.rng.uniform();
             p.rx = R * cos(phi);
             p.ry = R * sin(phi);
+        } else if constexpr (GRID == SKIRT_GRID_SPHERE1D) {
+            // Sphere1DDustGrid::randomPositionInCell: Random::direction() (two deviates), then r uniform in the shell
+            double ux, uy, uz;
+            isotropic(p.rng, ux, uy, uz);
+            const double* rv = sh.mesh;
+            const double rr = rv[m] + (rv[m + 1] - rv[m]) * p.rng.uniform();
+            p.rx = rr * ux; p.ry = rr * uy; p.rz = rr * uz;
+        } else if constexpr (GRID == SKIRT_GRID_SPHERE2D) {
+            // Sphere2DDustGrid::randomPositionInCell: three deviates in the order r, theta, phi
+            const double* rv = sh.mesh;
+            const double* thv = Grid<SKIRT_GRID_SPHERE2D>::thetaBorders(a, sh);
+            const int i = m / a.nz, k = m % a.nz;
+            const double ris = rv[i] * rv[i];
+            const double ri1s = rv[i + 1] * rv[i + 1];
+            const double rr = sqrt(ris + (ri1s - ris) * p.rng.uniform());
+            const double theta = thv[k] + (thv[k + 1] - thv[k]) * p.rng.uniform();
+            const double phi = 2.0 * M_PI * p.rng.uniform();
+            const double st = sin(theta);
+            p.rx = rr * st * cos(phi);
+            p.ry = rr * st * sin(phi);
+            p.rz = rr * cos(theta);
         } else {
             double b[6];
             cellBox(m, b);
@@ -3891,6 +4004,38 @@ int skirt_mcrt_upload_grid(SkirtMcrt* c, const SkirtGridDesc* g) {
         c->mapL = -1;
         int rc = upload(c, c->dMesh, mesh.data(), mesh.size());
         if (rc) return rc;
+    } else if (g->kind == SKIRT_GRID_SPHERE1D || g->kind == SKIRT_GRID_SPHERE2D) {
+        const bool two = g->kind == SKIRT_GRID_SPHERE2D;
+        const int nt = two ? g->nz : 0;
+        if (g->nx < 1 || !g->xv) return fail(c, SKIRT_ERR_ARG, "bad spherical grid");
+        if (two ? (nt < 1 || g->ny != nt || !g->yv || !g->zv) : (g->ny != 0 || g->nz != 0))
+            return fail(c, SKIRT_ERR_ARG, "bad spherical grid");
+        if ((long long)g->nx * (two ? nt : 1) != g->ncells) return fail(c, SKIRT_ERR_ARG, "ncells != nx*nz");
+        const double rmax = g->extent[3];
+        if (!(rmax > 0.0) || !(g->xv[g->nx - 1] < rmax)) return fail(c, SKIRT_ERR_ARG, "extent does not hold the outer radius");
+        if (g->xv[0] != 0.0) return fail(c, SKIRT_ERR_ARG, "the radial mesh does not start at 0");
+        for (int i = 0; i < g->nx; i++) if (!(g->xv[i] < g->xv[i + 1])) return fail(c, SKIRT_ERR_ARG, "r mesh not increasing");
+        for (int i = 0; i < nt; i++) if (!(g->zv[i] < g->zv[i + 1])) return fail(c, SKIRT_ERR_ARG, "theta mesh not increasing");
+        for (int i = 0; i < nt; i++) if (!(g->yv[i] > g->yv[i + 1])) return fail(c, SKIRT_ERR_ARG, "cosines not decreasing");
+        if (two && !(g->eps > 0.0)) return fail(c, SKIRT_ERR_ARG, "eps should be positive");
+        // r | cos theta | theta: the Cartesian mesh layout (one unused word each where ny = nz = 0)
+        std::vector<double> mesh;
+        mesh.insert(mesh.end(), g->xv, g->xv + g->nx + 1);
+        if (two) {
+            mesh.insert(mesh.end(), g->yv, g->yv + nt + 1);
+            mesh.insert(mesh.end(), g->zv, g->zv + nt + 1);
+        } else {
+            mesh.push_back(0.0);
+            mesh.push_back(0.0);
+        }
+        c->nx = g->nx; c->ny = nt; c->nz = nt;
+        c->gx0 = -rmax; c->gx1 = rmax;
+        c->gy0 = -rmax; c->gy1 = rmax;
+        c->gz0 = -rmax; c->gz1 = rmax;
+        c->eps = two ? g->eps : 0.0;
+        c->mapL = -1;
+        int rc = upload(c, c->dMesh, mesh.data(), mesh.size());
+        if (rc) return rc;
     } else {
         return fail(c, SKIRT_ERR_UNSUPPORTED, "unsupported grid kind");
     }
@@ -4496,7 +4641,8 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
     // LDS layout (doubles): mesh | optics | instruments | SED sums
     int off = 0;
     a.ldsMeshOff = off;
-    const bool meshGrid = c->gridKind == SKIRT_GRID_CARTESIAN || c->gridKind == SKIRT_GRID_CYLINDER2D;
+    const bool meshGrid = c->gridKind == SKIRT_GRID_CARTESIAN || c->gridKind == SKIRT_GRID_CYLINDER2D ||
+                          c->gridKind == SKIRT_GRID_SPHERE1D || c->gridKind == SKIRT_GRID_SPHERE2D;
     off += (meshGrid && a.hasDust) ? (c->nx + c->ny + c->nz + 3) : 0;
     off += leafMap ? 3 * (c->mapN + 1) : 0;
     off = (off + 1) & ~1;
@@ -4536,6 +4682,8 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
     const int kind = c->gridKind == SKIRT_GRID_CARTESIAN ? SKIRT_GRID_CARTESIAN
                      : c->gridKind == SKIRT_GRID_VORONOI ? SKIRT_GRID_VORONOI
                      : c->gridKind == SKIRT_GRID_CYLINDER2D ? SKIRT_GRID_CYLINDER2D
+                     : c->gridKind == SKIRT_GRID_SPHERE1D ? SKIRT_GRID_SPHERE1D
+                     : c->gridKind == SKIRT_GRID_SPHERE2D ? SKIRT_GRID_SPHERE2D
                      : bookkeeping ? kOctreeBookkeeping
                      : (leafMap ? (c->binTree ? kBinTreeMap : SKIRT_GRID_OCTREE) : kOctreeNodes);
     c->lastWalk = kind == SKIRT_GRID_CARTESIAN ? SKIRT_WALK_CARTESIAN
@@ -4544,6 +4692,8 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
                   : kind == kOctreeBookkeeping ? SKIRT_WALK_OCTREE_BOOKKEEPING
                   : kind == SKIRT_GRID_VORONOI ? SKIRT_WALK_VORONOI
                   : kind == SKIRT_GRID_CYLINDER2D ? SKIRT_WALK_CYLINDER2D
+                  : kind == SKIRT_GRID_SPHERE1D ? SKIRT_WALK_SPHERE1D
+                  : kind == SKIRT_GRID_SPHERE2D ? SKIRT_WALK_SPHERE2D
                                                : SKIRT_WALK_TREE_NODES;
     const bool one = a.ncomp == 1;
     const void* traceFn = nullptr;
@@ -4559,6 +4709,8 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
     else if (kind == kBinTreeMap) SKIRT_PICK(kBinTreeMap);
     else if (kind == kOctreeBookkeeping) SKIRT_PICK(kOctreeBookkeeping);
     else if (kind == SKIRT_GRID_CYLINDER2D) SKIRT_PICK(SKIRT_GRID_CYLINDER2D);
+    else if (kind == SKIRT_GRID_SPHERE1D) SKIRT_PICK(SKIRT_GRID_SPHERE1D);
+    else if (kind == SKIRT_GRID_SPHERE2D) SKIRT_PICK(SKIRT_GRID_SPHERE2D);
     else if (kind == SKIRT_GRID_VORONOI) {
         if (a.labsGlobal)
             pick(traceKernelVor<true, false, true>, traceKernelVor<false, false, true>, traceKernelVor<true, true, true>,
@@ -4604,6 +4756,8 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
         else if (kind == kBinTreeMap) { if (one) SKIRT_EVENT(kBinTreeMap, true); else SKIRT_EVENT(kBinTreeMap, false); }
         else if (kind == kOctreeBookkeeping) { if (one) SKIRT_EVENT(kOctreeBookkeeping, true); else SKIRT_EVENT(kOctreeBookkeeping, false); }
         else if (kind == SKIRT_GRID_CYLINDER2D) { if (one) SKIRT_EVENT(SKIRT_GRID_CYLINDER2D, true); else SKIRT_EVENT(SKIRT_GRID_CYLINDER2D, false); }
+        else if (kind == SKIRT_GRID_SPHERE1D) { if (one) SKIRT_EVENT(SKIRT_GRID_SPHERE1D, true); else SKIRT_EVENT(SKIRT_GRID_SPHERE1D, false); }
+        else if (kind == SKIRT_GRID_SPHERE2D) { if (one) SKIRT_EVENT(SKIRT_GRID_SPHERE2D, true); else SKIRT_EVENT(SKIRT_GRID_SPHERE2D, false); }
         else if (kind == SKIRT_GRID_VORONOI) { if (one) SKIRT_EVENT(SKIRT_GRID_VORONOI, true); else SKIRT_EVENT(SKIRT_GRID_VORONOI, false); }
         else { if (one) SKIRT_EVENT(kOctreeNodes, true); else SKIRT_EVENT(kOctreeNodes, false); }
 #undef SKIRT_EVENT
@@ -4615,6 +4769,8 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
         else if (kind == kBinTreeMap) { if (one) SKIRT_CONT(kBinTreeMap, true); else SKIRT_CONT(kBinTreeMap, false); }
         else if (kind == kOctreeBookkeeping) { if (one) SKIRT_CONT(kOctreeBookkeeping, true); else SKIRT_CONT(kOctreeBookkeeping, false); }
         else if (kind == SKIRT_GRID_CYLINDER2D) { if (one) SKIRT_CONT(SKIRT_GRID_CYLINDER2D, true); else SKIRT_CONT(SKIRT_GRID_CYLINDER2D, false); }
+        else if (kind == SKIRT_GRID_SPHERE1D) { if (one) SKIRT_CONT(SKIRT_GRID_SPHERE1D, true); else SKIRT_CONT(SKIRT_GRID_SPHERE1D, false); }
+        else if (kind == SKIRT_GRID_SPHERE2D) { if (one) SKIRT_CONT(SKIRT_GRID_SPHERE2D, true); else SKIRT_CONT(SKIRT_GRID_SPHERE2D, false); }
         else if (kind == SKIRT_GRID_VORONOI) { if (one) SKIRT_CONT(SKIRT_GRID_VORONOI, true); else SKIRT_CONT(SKIRT_GRID_VORONOI, false); }
         else { if (one) SKIRT_CONT(kOctreeNodes, true); else SKIRT_CONT(kOctreeNodes, false); }
 #undef SKIRT_CONT
@@ -4883,6 +5039,12 @@ int skirt_mcrt_column_densities(SkirtMcrt* c, const double* rays, int n, double*
                                (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
         else if (c->gridKind == SKIRT_GRID_CYLINDER2D)
             hipLaunchKernelGGL(columnKernel<SKIRT_GRID_CYLINDER2D>, grid, dim3(kBlock),
+                               (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
+        else if (c->gridKind == SKIRT_GRID_SPHERE1D)
+            hipLaunchKernelGGL(columnKernel<SKIRT_GRID_SPHERE1D>, grid, dim3(kBlock),
+                               (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
+        else if (c->gridKind == SKIRT_GRID_SPHERE2D)
+            hipLaunchKernelGGL(columnKernel<SKIRT_GRID_SPHERE2D>, grid, dim3(kBlock),
                                (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
         else if (c->gridKind == SKIRT_GRID_VORONOI)
             hipLaunchKernelGGL(columnKernel<SKIRT_GRID_VORONOI>, grid, dim3(kBlock), 0, c->stream, a, d, n, d + 6 * (size_t)n);

@@ -359,6 +359,8 @@ double WavelengthGrid::lambdamax(int ell) const {
 
 void DustGrid::cellBox(int m, double b[6]) const {
     if (kind == GridKind::Cylinder2D) throw std::runtime_error("a cylindrical dust cell has no Cartesian box");
+    if (kind == GridKind::Sphere1D || kind == GridKind::Sphere2D)
+        throw std::runtime_error("a spherical dust cell has no Cartesian box");
     if (kind == GridKind::Voronoi) {
         for (int q = 0; q < 6; q++) b[q] = vor.bbox[6 * (size_t)m + q];
         return;
@@ -385,6 +387,18 @@ void DustGrid::cellCenter(int m, double c[3]) const {
         c[0] = R * std::cos(phi); c[1] = R * std::sin(phi); c[2] = (cyl.zv[k] + cyl.zv[k + 1]) / 2.0;
         return;
     }
+    if (kind == GridKind::Sphere1D) {  // Sphere1DDustGrid::centralPositionInCell: Position(r, 0, 0)
+        c[0] = (sph.rv[m] + sph.rv[m + 1]) / 2.0; c[1] = 0; c[2] = 0;
+        return;
+    }
+    if (kind == GridKind::Sphere2D) {  // Sphere2DDustGrid::centralPositionInCell: Position(r, theta, 0, SPHERICAL)
+        const int i = m / sph.Ntheta, k = m % sph.Ntheta;
+        const double r = (sph.rv[i] + sph.rv[i + 1]) / 2.0;
+        const double theta = (sph.thetav[k] + sph.thetav[k + 1]) / 2.0, phi = 0.0;
+        const double costheta = std::cos(theta), sintheta = std::sin(theta);
+        c[0] = r * sintheta * std::cos(phi); c[1] = r * sintheta * std::sin(phi); c[2] = r * costheta;
+        return;
+    }
     double b[6];
     cellBox(m, b);
     for (int q = 0; q < 3; q++) c[q] = 0.5 * (b[q] + b[3 + q]);
@@ -395,6 +409,15 @@ double DustGrid::cellVolume(int m) const {
     if (kind == GridKind::Cylinder2D) {  // Cylinder2DDustGrid::volume
         const int i = m / cyl.Nz, k = m % cyl.Nz;
         return M_PI * (cyl.zv[k + 1] - cyl.zv[k]) * (cyl.Rv[i + 1] - cyl.Rv[i]) * (cyl.Rv[i + 1] + cyl.Rv[i]);
+    }
+    if (kind == GridKind::Sphere1D) {  // Sphere1DDustGrid::volume
+        const double rL = sph.rv[m], rR = sph.rv[m + 1];
+        return 4.0 * M_PI / 3.0 * (rR - rL) * (rR * rR + rR * rL + rL * rL);
+    }
+    if (kind == GridKind::Sphere2D) {  // Sphere2DDustGrid::volume (the cosines of theta, not the fixed-up array)
+        const int i = m / sph.Ntheta, k = m % sph.Ntheta;
+        return (2.0 / 3.0) * M_PI * (std::pow(sph.rv[i + 1], 3) - std::pow(sph.rv[i], 3)) *
+               (std::cos(sph.thetav[k]) - std::cos(sph.thetav[k + 1]));
     }
     double b[6];
     cellBox(m, b);
@@ -407,6 +430,14 @@ int DustGrid::whichcell(double x, double y, double z) const {
         int i = nr::locateFail(cyl.Rv, std::sqrt(x * x + y * y)), k = nr::locateFail(cyl.zv, z);
         if (i < 0 || k < 0) return -1;
         return k + cyl.Nz * i;
+    }
+    if (kind == GridKind::Sphere1D) return nr::locateFail(sph.rv, std::sqrt(x * x + y * y + z * z));
+    if (kind == GridKind::Sphere2D) {  // Sphere2DDustGrid::whichcell (Position::spherical: theta = 0 at r = 0)
+        const double r = std::sqrt(x * x + y * y + z * z);
+        const double theta = r == 0 ? 0.0 : std::acos(z / r);
+        const int i = nr::locateFail(sph.rv, r);
+        if (i < 0) return -1;
+        return nr::locateClip(sph.thetav, theta) + sph.Ntheta * i;
     }
     if (kind == GridKind::Cartesian) {
         int i = nr::locateFail(cart.xv, x), j = nr::locateFail(cart.yv, y), k = nr::locateFail(cart.zv, z);
@@ -1596,6 +1627,46 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
             for (int i = 0; i <= g.NR; i++) g.Rv[i] = tR[i] * g.Rmax;
             for (int k = 0; k <= g.Nz; k++) g.zv[k] = tz[k] * (g.zmax - g.zmin) + g.zmin;
             m.grid.ncells = g.NR * g.Nz;
+        } else if (ge->name == "Sphere1DDustGrid" || ge->name == "Sphere2DDustGrid") {
+            // SphereDustGrid::setupSelfBefore, Sphere1DDustGrid::setupSelfAfter, Sphere2DDustGrid::setupSelfAfter
+            const bool two = ge->name == "Sphere2DDustGrid";
+            m.grid.kind = two ? GridKind::Sphere2D : GridKind::Sphere1D;
+            SphereGrid& g = m.grid.sph;
+            g.rmax = attr(c, ge, "maxR", "length", 0);
+            if (g.rmax <= 0) throw std::runtime_error("The outer radius of the grid should be positive");
+            const std::vector<double> tr = unitMesh(c, need(ge, "meshR"), g.Nr, true);
+            g.rv.resize(g.Nr + 1);
+            for (int i = 0; i <= g.Nr; i++) g.rv[i] = tr[i] * g.rmax;
+            m.grid.ncells = g.Nr;
+            if (two) {
+                const std::vector<double> tt = unitMesh(c, need(ge, "meshTheta"), g.Ntheta, false);
+                g.thetav.resize(g.Ntheta + 1);
+                g.cv.resize(g.Ntheta + 1);
+                for (int k = 0; k <= g.Ntheta; k++) g.thetav[k] = tt[k] * M_PI;
+                for (int k = 0; k <= g.Ntheta; k++) g.cv[k] = std::cos(g.thetav[k]);
+                g.cv[0] = 1.;
+                g.cv[g.Ntheta] = -1.;
+                // path() needs a border at pi/2: a cosine close to zero becomes exactly zero, else one is inserted
+                int numzeroes = 0;
+                for (int k = 1; k < g.Ntheta; k++)
+                    if (std::fabs(g.cv[k]) < 1e-9) {
+                        numzeroes++;
+                        g.cv[k] = 0.;
+                    }
+                if (numzeroes > 1) throw std::runtime_error("There are multiple grid points very close to pi/2");
+                if (numzeroes == 0) {
+                    const std::vector<double> orTheta = g.thetav, orC = g.cv;
+                    g.Ntheta++;
+                    g.thetav.assign(g.Ntheta + 1, M_PI_2);
+                    g.cv.assign(g.Ntheta + 1, 0.0);
+                    for (int k = 0; k < g.Ntheta; k++) {
+                        const int target = (orC[k] > 0) ? k : k + 1;
+                        g.thetav[target] = orTheta[k];
+                        g.cv[target] = orC[k];
+                    }
+                }
+                m.grid.ncells = g.Nr * g.Ntheta;
+            }
         } else {
             throw std::runtime_error("unsupported dust grid " + ge->name);
         }
@@ -1690,6 +1761,47 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
                     const double phi = 2.0 * M_PI * u[3 * n + 1];
                     const double z = g.zv[k] + (g.zv[k + 1] - g.zv[k]) * u[3 * n + 2];
                     const double x = R * std::cos(phi), y = R * std::sin(phi);
+                    for (int h = 0; h < Ncomp; h++) sumv[h] += m.dust[h].density(x, y, z);
+                }
+                for (int h = 0; h < Ncomp; h++) m.rho[cell * Ncomp + h] = 1.0 * sumv[h] / m.sampleCount;
+            });
+        } else if (m.grid.kind == GridKind::Sphere1D) {
+            // Sphere1DDustGrid::randomPositionInCell per sample: Random::direction() (theta, phi), then r uniform
+            // in the shell; always on the host, like the cylinder's
+            const SphereGrid& g = m.grid.sph;
+            parallelDraws(rng, (size_t)Ncells, 3 * m.sampleCount, [&](size_t cell, const double* u) {
+                const int i = (int)cell;
+                std::vector<double> sumv(Ncomp, 0.0);
+                for (int n = 0; n < m.sampleCount; n++) {
+                    const double theta = std::acos(2.0 * u[3 * n] - 1.0);
+                    const double phi = 2.0 * M_PI * u[3 * n + 1];
+                    double kx, ky, kz;  // Direction::Direction(theta, phi)
+                    if (theta <= 1e-8) { kx = 0; ky = 0; kz = 1; }
+                    else if (theta >= M_PI - 1e-8) { kx = 0; ky = 0; kz = -1; }
+                    else {
+                        const double sintheta = std::sin(theta);
+                        kx = sintheta * std::cos(phi); ky = sintheta * std::sin(phi); kz = std::cos(theta);
+                    }
+                    const double r = g.rv[i] + (g.rv[i + 1] - g.rv[i]) * u[3 * n + 2];
+                    for (int h = 0; h < Ncomp; h++) sumv[h] += m.dust[h].density(r * kx, r * ky, r * kz);
+                }
+                for (int h = 0; h < Ncomp; h++) m.rho[cell * Ncomp + h] = 1.0 * sumv[h] / m.sampleCount;
+            });
+        } else if (m.grid.kind == GridKind::Sphere2D) {
+            // Sphere2DDustGrid::randomPositionInCell per sample: r, theta, phi, then Position(.., SPHERICAL)
+            const SphereGrid& g = m.grid.sph;
+            parallelDraws(rng, (size_t)Ncells, 3 * m.sampleCount, [&](size_t cell, const double* u) {
+                const int i = (int)cell / g.Ntheta, k = (int)cell % g.Ntheta;
+                const double ris = g.rv[i] * g.rv[i];
+                const double ri1s = g.rv[i + 1] * g.rv[i + 1];
+                std::vector<double> sumv(Ncomp, 0.0);
+                for (int n = 0; n < m.sampleCount; n++) {
+                    const double r = std::sqrt(ris + (ri1s - ris) * u[3 * n]);
+                    const double theta = g.thetav[k] + (g.thetav[k + 1] - g.thetav[k]) * u[3 * n + 1];
+                    const double phi = 2.0 * M_PI * u[3 * n + 2];
+                    const double costheta = std::cos(theta), sintheta = std::sin(theta);
+                    const double cosphi = std::cos(phi), sinphi = std::sin(phi);
+                    const double x = r * sintheta * cosphi, y = r * sintheta * sinphi, z = r * costheta;
                     for (int h = 0; h < Ncomp; h++) sumv[h] += m.dust[h].density(x, y, z);
                 }
                 for (int h = 0; h < Ncomp; h++) m.rho[cell * Ncomp + h] = 1.0 * sumv[h] / m.sampleCount;

@@ -41,6 +41,17 @@ void writeGrid(Writer& w, const SkirtGridDesc& g) {
         w.i1("grid.nz", g.nz);
         w.d("grid.xv", g.xv, (size_t)g.nx + 1);
         w.d("grid.zv", g.zv, (size_t)g.nz + 1);
+    } else if (g.kind == SKIRT_GRID_SPHERE1D || g.kind == SKIRT_GRID_SPHERE2D) {
+        w.i1("grid.nx", g.nx);
+        w.d("grid.xv", g.xv, (size_t)g.nx + 1);
+        if (g.kind == SKIRT_GRID_SPHERE2D) {
+            w.i1("grid.ny", g.ny);
+            w.i1("grid.nz", g.nz);
+            w.d("grid.yv", g.yv, (size_t)g.ny + 1);
+            w.d("grid.zv", g.zv, (size_t)g.nz + 1);
+            w.d1("grid.eps", g.eps);
+        }
+        w.d("grid.extent", g.extent, 6);
     } else if (g.kind == SKIRT_GRID_OCTREE) {
         const size_t n = (size_t)g.nnodes;
         w.i1("grid.nnodes", g.nnodes);

@@ -159,7 +159,17 @@ struct Cylinder2DGrid {
     std::vector<double> Rv, zv;  // NR+1 radial borders (Rv[0] = 0), Nz+1 z borders
 };
 
-enum class GridKind : int { Cartesian = 0, Octree = 1, Voronoi = 2, Cylinder2D = 3 };
+// Spherical grids: SKIRTcore/Sphere1DDustGrid.cpp (shells, cell m = i) and Sphere2DDustGrid.cpp (shells x polar
+// bins, cell m = k + Ntheta*i), both on SphereDustGrid.cpp. Ntheta = 0 for the 1D grid.
+struct SphereGrid {
+    int Nr = 0, Ntheta = 0;
+    double rmax = 0;
+    std::vector<double> rv;      // Nr+1 radial borders (mesh * rmax; a LogMesh's last may miss rmax by a bit)
+    std::vector<double> thetav;  // 2D: Ntheta+1 polar borders, a border pi/2 inserted where the mesh has none
+    std::vector<double> cv;      // 2D: their cosines, with exact 1, 0, -1 (Sphere2DDustGrid::setupSelfAfter)
+};
+
+enum class GridKind : int { Cartesian = 0, Octree = 1, Voronoi = 2, Cylinder2D = 3, Sphere1D = 4, Sphere2D = 5 };
 
 struct DustGrid {
     GridKind kind = GridKind::Cartesian;
@@ -167,12 +177,13 @@ struct DustGrid {
     OctreeGrid tree;
     VoronoiGrid vor;
     Cylinder2DGrid cyl;
+    SphereGrid sph;
     int ncells = 0;
-    // xmin ymin zmin xmax ymax zmax (Voronoi: the enclosing box; not defined for a cylindrical grid)
+    // xmin ymin zmin xmax ymax zmax (Voronoi: the enclosing box; not defined for a cylindrical or spherical grid)
     void cellBox(int m, double b[6]) const;
     double cellVolume(int m) const;
     // DustGrid::centralPositionInCell: the box centre, the centroid of a Voronoi cell, or (R, phi = 0, z) at the
-    // middle of a cylindrical cell's borders
+    // middle of a cylindrical cell's borders, or (r, theta, phi = 0) at the middle of a spherical cell's
     void cellCenter(int m, double c[3]) const;
     int whichcell(double x, double y, double z) const;
 };

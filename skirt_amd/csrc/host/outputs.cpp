@@ -309,9 +309,11 @@ void writeOutputs(const Model& m, const std::string& prefix, const std::vector<s
             tauV[c] = tau;
         }
         // The statistics lines that close the reference's file (DustSystem.cpp:663-687), for the cylindrical
-        // grid, whose file then equals the reference's byte for byte. The files of the grid kinds that came
-        // before it keep their form (rows only).
-        if (m.grid.kind == GridKind::Cylinder2D && Ncells > 0) {
+        // and spherical grids, whose file then equals the reference's byte for byte. The files of the grid kinds
+        // that came before them keep their form (rows only).
+        const bool closing = m.grid.kind == GridKind::Cylinder2D || m.grid.kind == GridKind::Sphere1D ||
+                             m.grid.kind == GridKind::Sphere2D;
+        if (closing && Ncells > 0) {
             double tausum = 0;
             for (double t : tauV) tausum += t;
             const double tauavg = tausum / Ncells;

@@ -192,7 +192,9 @@ int skirt_sim_info(SkirtSim* s, SkirtSimInfo* o) {
     o->ninstruments = (int)s->m.instruments.size();
     o->grid_kind = s->m.grid.kind == GridKind::Octree ? SKIRT_GRID_OCTREE
                    : s->m.grid.kind == GridKind::Voronoi ? SKIRT_GRID_VORONOI
-                   : s->m.grid.kind == GridKind::Cylinder2D ? SKIRT_GRID_CYLINDER2D : SKIRT_GRID_CARTESIAN;
+                   : s->m.grid.kind == GridKind::Cylinder2D ? SKIRT_GRID_CYLINDER2D
+                   : s->m.grid.kind == GridKind::Sphere1D ? SKIRT_GRID_SPHERE1D
+                   : s->m.grid.kind == GridKind::Sphere2D ? SKIRT_GRID_SPHERE2D : SKIRT_GRID_CARTESIAN;
     o->nnodes = s->m.grid.kind == GridKind::Octree ? s->m.grid.tree.nnodes() : 0;
     o->npp = s->npp;
     o->total_packets = s->npp * (uint64_t)s->m.wl.n();
@@ -250,6 +252,16 @@ void buildDescs(const Model& m, Descs& d) {
             g.kind = SKIRT_GRID_CYLINDER2D;
             g.nx = m.grid.cyl.NR; g.ny = 0; g.nz = m.grid.cyl.Nz;
             g.xv = m.grid.cyl.Rv.data(); g.zv = m.grid.cyl.zv.data();
+        } else if (m.grid.kind == GridKind::Sphere1D || m.grid.kind == GridKind::Sphere2D) {
+            // r borders in xv; 2D: the fixed-up cosines in yv and the polar borders in zv; extent carries maxR
+            const SphereGrid& sg = m.grid.sph;
+            const bool two = m.grid.kind == GridKind::Sphere2D;
+            g.kind = two ? SKIRT_GRID_SPHERE2D : SKIRT_GRID_SPHERE1D;
+            g.nx = sg.Nr; g.ny = sg.Ntheta; g.nz = sg.Ntheta;
+            g.xv = sg.rv.data();
+            if (two) { g.yv = sg.cv.data(); g.zv = sg.thetav.data(); }
+            for (int q = 0; q < 3; q++) { g.extent[q] = -sg.rmax; g.extent[3 + q] = sg.rmax; }
+            if (two) g.eps = 1e-11 * sg.rmax;
         } else {
             const OctreeGrid& t = m.grid.tree;
             g.kind = SKIRT_GRID_OCTREE;
