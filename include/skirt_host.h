@@ -114,6 +114,12 @@ int skirt_sim_describe(SkirtSim* sim, const char* path);
 int skirt_host_write_descriptors(const char* path, const SkirtGridDesc* grid, const SkirtMediaDesc* media,
                                  const SkirtSourceDesc* sources, const SkirtInstrDesc* instr, int ninstr);
 
+/* Random positions of stellar component `comp` (skirt_mcrt_sample_positions): on the attached engine of HIP
+ * device `device` (which must be the device of skirt_sim_attach), or with device < 0 on the host, through the
+ * host's position templates on the same per-packet streams. pos is n x 3, draws n (or NULL). */
+int skirt_sim_sample_positions(SkirtSim* sim, int comp, int device, uint64_t seed, uint64_t first, size_t n,
+                               double* pos, int32_t* draws);
+
 /* The cross-GPU sums in C++: RCCL (NCCL API) all-reduces over xGMI, the MI355X counterpart of the
  * reference's MPI_Allreduce of the absorption tables and instrument arrays (PanDustSystem.cpp:394-404,
  * Instrument.cpp:57-66, MPIsupport/ProcessManager.cpp:133-137).

@@ -52,7 +52,9 @@ enum {
 enum { SKIRT_GRID_CARTESIAN = 0, SKIRT_GRID_OCTREE = 1, SKIRT_GRID_VORONOI = 2, SKIRT_GRID_CYLINDER2D = 3,
        SKIRT_GRID_SPHERE1D = 4, SKIRT_GRID_SPHERE2D = 5 };
 enum { SKIRT_TREE_TOPDOWN = 0, SKIRT_TREE_NEIGHBOR = 1, SKIRT_TREE_BOOKKEEPING = 2 /* octrees only */ };
-enum { SKIRT_GEOM_PLUMMER = 0, SKIRT_GEOM_EXPDISK = 1, SKIRT_GEOM_SERSIC = 2, SKIRT_GEOM_POINT = 3 };
+enum { SKIRT_GEOM_PLUMMER = 0, SKIRT_GEOM_EXPDISK = 1, SKIRT_GEOM_SERSIC = 2, SKIRT_GEOM_POINT = 3,
+       SKIRT_GEOM_SHELL = 4, SKIRT_GEOM_GAMMA = 5, SKIRT_GEOM_GAUSSIAN = 6, SKIRT_GEOM_TTAURIDISK = 7,
+       SKIRT_GEOM_TORUS = 8, SKIRT_GEOM_CONICALSHELL = 9 };
 enum { SKIRT_INSTR_FULL = 0, SKIRT_INSTR_SIMPLE = 1, SKIRT_INSTR_SED = 2, SKIRT_INSTR_FRAME = 3 };
 enum { SKIRT_PHASE_STELLAR = 0, SKIRT_PHASE_DUST_EMISSION = 1, SKIRT_PHASE_DUST_SELFABS = 2 };
 
@@ -122,13 +124,22 @@ typedef struct {
     const int* geom_kind;       /* ncomp, SKIRT_GEOM_* */
     const double* geom_param;   /* ncomp x 8: PlummerGeometry {c, rho0, 0...};
                                    ExpDiskGeometry {hR, hz, Rmax, zmax, Rmin, rho0, 0, 0};
-                                   SersicGeometry {reff, n, rho0, 0...} (tables in geom_table) */
+                                   SersicGeometry {reff, n, rho0, 0...} (tables in geom_table);
+                                   ShellGeometry {rmin, rmax, p, smin, sdiff, A, 0, 0};
+                                   GammaGeometry {b, gamma, rho0, 0...};
+                                   GaussianGeometry {sigma, q, rho0, 0...};
+                                   TTauriDiskGeometry {Rinn, Rout, Rd, zd, rho0, 0, 0, 0};
+                                   TorusGeometry and ConicalShellGeometry {p, q, rmin, rmax, rani (0 or 1),
+                                   rcut, A, 0} (the rest in geom_table). The eighth word is the engine's. */
     const double* lum;          /* ncomp x nlambda, W */
     const double* lumtot;       /* nlambda, sum over components */
     const double* cdf;          /* nlambda x (ncomp+1) normalized cumulative luminosity */
     double emission_bias;
     const double* geom_table;   /* ncomp x 202 (NULL if no component needs it): SersicGeometry's
-                                   SersicFunction tables {s_0..s_100, M_0..M_100} */
+                                   SersicFunction tables {s_0..s_100, M_0..M_100}; TorusGeometry's
+                                   {sinDelta, -1, smin, sdiff, 0...}; ConicalShellGeometry's
+                                   {sinDeltaOut, sinDeltaIn, smin, sdiff, 0...} (the -1 stands for the inner
+                                   angle the torus lacks: no |cos theta| lies at or below it) */
 } SkirtSourceDesc;
 
 /* Distant instruments (DistantInstrument.cpp:27-50, SingleFrameInstrument.cpp:24-38, 130-147). */
@@ -294,7 +305,8 @@ int skirt_mcrt_synchronize(SkirtMcrt* ctx);
  *                          total density (TreeNodeSampleDensityCalculator: mass, barycentre and density
  *                          dispersion of a tree node, TreeDustGrid.cpp:174-222)
  * The density of component h is norm[h] times its geometry's (PlummerGeometry / ExpDiskGeometry /
- * SersicGeometry / PointGeometry::density), in the host's operation order; the device's exp, pow and log10
+ * SersicGeometry / PointGeometry / ShellGeometry / GammaGeometry / GaussianGeometry / TTauriDiskGeometry /
+ * TorusGeometry / ConicalShellGeometry::density), in the host's operation order; the device's exp, pow and log10
  * may differ from the host's by an ulp. Synchronous. */
 enum { SKIRT_DENS_COMPONENTS = 0, SKIRT_DENS_NODE = 1 };
 typedef struct {
@@ -302,11 +314,22 @@ typedef struct {
     const int* geom_kind;       /* ncomp, SKIRT_GEOM_* */
     const double* geom_param;   /* ncomp x 8, laid out as SkirtSourceDesc::geom_param */
     const double* norm;         /* ncomp: the component's normalization (its dust mass) */
-    const double* dens_table;   /* ncomp x 2*ntab (NULL if no SersicGeometry): SersicFunction s_i, then S(s_i) */
+    const double* dens_table;   /* ncomp x 2*ntab (NULL if no component needs it; ntab >= 2): SersicFunction s_i,
+                                   then S(s_i); a TorusGeometry's or ConicalShellGeometry's row starts with the
+                                   four words of its SkirtSourceDesc::geom_table row */
     int ntab;
 } SkirtDensityDesc;
 int skirt_mcrt_sample_density(int device, const SkirtDensityDesc* dens, const double* boxes, size_t n,
                               const uint32_t* words, int nsample, int mode, double* out);
+
+/* Geometry::generatePosition of source component `comp` of the uploaded sources, as the event kernel's launch
+ * runs it: packet first + i draws from a fresh stream PacketRng::start(seed, SKIRT_POSITIONS_TAG, first + i)
+ * (a tag no photon phase uses); pos[3 i ..] receives its position and draws[i] (if not NULL) the number of
+ * uniform deviates it consumed. A TorusGeometry or ConicalShellGeometry whose rejection loop ends at its cap of
+ * 2^16 attempts fails the call with SKIRT_ERR_NUMERIC. Synchronous. */
+#define SKIRT_POSITIONS_TAG 0x504f5331u
+int skirt_mcrt_sample_positions(SkirtMcrt* ctx, int comp, uint64_t seed, uint64_t first, size_t n, double* pos,
+                                int32_t* draws);
 
 /* The cells of a Voronoi tessellation on HIP device `device` (setup, §8(f)2; the reference computes them with
  * Voro++, VoronoiMesh.cpp:310-376): the host construction of skirt_host_voronoi_build (the domain box clipped

@@ -12,11 +12,14 @@
 #include "Cylinder2DDustGrid.hpp"
 #include "DistantInstrument.hpp"
 #include "DustMix.hpp"
+#include "ConicalShellGeometry.hpp"
 #include "DustSystem.hpp"
 #include "ExpDiskGeometry.hpp"
 #include "FatalError.hpp"
 #include "FrameInstrument.hpp"
 #include "FullInstrument.hpp"
+#include "GammaGeometry.hpp"
+#include "GaussianGeometry.hpp"
 #include "GeometricStellarComp.hpp"
 #include "InstrumentSystem.hpp"
 #include "MoveableMesh.hpp"
@@ -27,10 +30,13 @@
 #include "SEDInstrument.hpp"
 #include "SersicFunction.hpp"
 #include "SersicGeometry.hpp"
+#include "ShellGeometry.hpp"
 #include "SimpleInstrument.hpp"
 #include "Sphere1DDustGrid.hpp"
 #include "Sphere2DDustGrid.hpp"
 #include "StellarSystem.hpp"
+#include "TTauriDiskGeometry.hpp"
+#include "TorusGeometry.hpp"
 #include "TreeDustGrid.hpp"
 #include "TreeNode.hpp"
 #include "VoronoiDustGrid.hpp"
@@ -435,6 +441,74 @@ void GpuPhotonEngine::describeSources()
         else if (dynamic_cast<PointGeometry*>(geo))
         {
             kind[h] = SKIRT_GEOM_POINT;
+        }
+        else if (ShellGeometry* shg = dynamic_cast<ShellGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_SHELL;
+            p[0] = shg->minRadius();
+            p[1] = shg->maxRadius();
+            p[2] = shg->expon();
+            p[3] = shg->_smin;  // ShellGeometry::setupSelfBefore (no public getters)
+            p[4] = shg->_sdiff;
+            p[5] = shg->_A;
+        }
+        else if (GammaGeometry* gg = dynamic_cast<GammaGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_GAMMA;
+            p[0] = gg->scale();
+            p[1] = gg->gamma();
+            p[2] = gg->_rho0;
+        }
+        else if (GaussianGeometry* gsg = dynamic_cast<GaussianGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_GAUSSIAN;
+            p[0] = gsg->dispersion();
+            p[1] = gsg->flattening();
+            p[2] = gsg->_rho0;
+        }
+        else if (TTauriDiskGeometry* tg = dynamic_cast<TTauriDiskGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_TTAURIDISK;
+            p[0] = tg->minRadius();
+            p[1] = tg->maxRadius();
+            p[2] = tg->radialScale();
+            p[3] = tg->axialScale();
+            p[4] = tg->_rho0;
+        }
+        else if (TorusGeometry* trg = dynamic_cast<TorusGeometry*>(geo))
+        {
+            // the engine supports no RotateGeometryDecorator, so _beta is 0 wherever this is reached
+            kind[h] = SKIRT_GEOM_TORUS;
+            p[0] = trg->expon();
+            p[1] = trg->index();
+            p[2] = trg->minRadius();
+            p[3] = trg->maxRadius();
+            p[4] = trg->anisoRadius() ? 1. : 0.;
+            p[5] = trg->cutRadius();
+            p[6] = trg->_A;
+            table.resize(202 * static_cast<size_t>(Ncomp), 0.);
+            double* t = &table[202 * static_cast<size_t>(h)];
+            t[0] = trg->_sinDelta;
+            t[1] = -1.;  // no inner angle (skirt_mcrt.h)
+            t[2] = trg->_smin;
+            t[3] = trg->_sdiff;
+        }
+        else if (ConicalShellGeometry* cg = dynamic_cast<ConicalShellGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_CONICALSHELL;
+            p[0] = cg->expon();
+            p[1] = cg->index();
+            p[2] = cg->minRadius();
+            p[3] = cg->maxRadius();
+            p[4] = cg->anisoRadius() ? 1. : 0.;
+            p[5] = cg->cutRadius();
+            p[6] = cg->_A;
+            table.resize(202 * static_cast<size_t>(Ncomp), 0.);
+            double* t = &table[202 * static_cast<size_t>(h)];
+            t[0] = cg->_sinDeltaOut;
+            t[1] = cg->_sinDeltaIn;
+            t[2] = cg->_smin;
+            t[3] = cg->_sdiff;
         }
         else
         {

@@ -25,6 +25,9 @@ LIB_PATH = os.path.join(PKG_DIR, os.environ.get("SKIRT_AMD_LIB", "libskirt_amd.s
 DATA_DIR = os.path.join(PKG_DIR, "data")
 
 GRID_CARTESIAN, GRID_OCTREE, GRID_VORONOI, GRID_CYLINDER2D, GRID_SPHERE1D, GRID_SPHERE2D = 0, 1, 2, 3, 4, 5
+# SKIRT_GEOM_*: the geometry kinds of stellar and dust components
+(GEOM_PLUMMER, GEOM_EXPDISK, GEOM_SERSIC, GEOM_POINT, GEOM_SHELL, GEOM_GAMMA, GEOM_GAUSSIAN, GEOM_TTAURIDISK,
+ GEOM_TORUS, GEOM_CONICALSHELL) = range(10)
 # SkirtStats.grid_walk: the trace kernel's grid walk in the last run (SKIRT_WALK_*)
 WALK_CARTESIAN, WALK_OCTREE_MAP, WALK_VORONOI, WALK_TREE_NODES, WALK_KDTREE_MAP, WALK_OCTREE_BOOKKEEPING = 0, 1, 2, 3, 4, 5
 
@@ -72,6 +75,7 @@ ABI_SYMBOLS = [
     "skirt_mcrt_set_crossed", "skirt_mcrt_download_crossed", "skirt_mcrt_column_densities",
     "skirt_rccl_create", "skirt_rccl_wrap", "skirt_rccl_rank", "skirt_rccl_reducer", "skirt_rccl_abort", "skirt_rccl_destroy", "skirt_sim_describe", "skirt_host_write_descriptors",
     "skirt_sim_run_devices", "skirt_mcrt_voronoi_cells", "skirt_host_voronoi_build_ex", "skirt_host_voronoi_cells",
+    "skirt_mcrt_sample_positions", "skirt_sim_sample_positions",
 ]
 
 _lib = None
@@ -127,6 +131,11 @@ def lib():
         L.skirt_sim_set_tallies.argtypes = [vp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl)]
         L.skirt_sim_write.argtypes = [vp, ctypes.c_char_p]
         L.skirt_sim_describe.argtypes = [vp, ctypes.c_char_p]
+        if hasattr(L, "skirt_sim_sample_positions"):  # (an older build chosen by SKIRT_AMD_LIB lacks them)
+            L.skirt_sim_sample_positions.argtypes = [vp, c_int, c_int, c_u64, c_u64, ctypes.c_size_t,
+                                                     ctypes.POINTER(c_dbl), ctypes.POINTER(ctypes.c_int32)]
+            L.skirt_mcrt_sample_positions.argtypes = [vp, c_int, c_u64, c_u64, ctypes.c_size_t, ctypes.POINTER(c_dbl),
+                                                      ctypes.POINTER(ctypes.c_int32)]
         L.skirt_sim_error.restype = ctypes.c_char_p
         L.skirt_sim_free.argtypes = [vp]
         L.skirt_mcrt_stats.argtypes = [vp, ctypes.POINTER(SkirtStats)]
@@ -304,6 +313,21 @@ class Simulation:
         self._check_engine(lib().skirt_mcrt_column_densities(self.engine, r.ctypes.data_as(dp), len(r),
                                                              out.ctypes.data_as(dp)))
         return out
+
+    def positions(self, comp, n, seed=1, first=0, device=None):
+        """n random positions of stellar component `comp` (Geometry::generatePosition) on the per-packet streams
+        first .. first + n - 1 of `seed`: (pos [n, 3], draws [n], the uniform deviates each consumed). device=None
+        runs the host's routines; a device runs the engine's launch routine there (attaching to it when no engine
+        is attached yet)."""
+        n = int(n)
+        pos = np.zeros((n, 3))
+        draws = np.zeros(n, dtype=np.int32)
+        if device is not None and not self.attached:
+            self.attach(int(device))
+        self._check(lib().skirt_sim_sample_positions(
+            self._h, int(comp), -1 if device is None else int(device), int(seed), int(first), n,
+            pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), draws.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return pos, draws
 
     def stats(self):
         s = SkirtStats()

@@ -35,6 +35,7 @@
 #include "vor_terms.hpp"
 #include "cyl2d_walk.hpp"
 #include "sph_walk.hpp"
+#include "geom_sample.hpp"
 #include "../../../include/skirt_mcrt.h"
 #include "philox.hpp"
 
@@ -64,6 +65,8 @@ constexpr int kCtrStride = 32;
 constexpr int kCtrWords = 16 * kCtrStride;
 #define CTR(base, k) ((base)[(k) * kCtrStride])
 #define CTRP(base, k) ((base) + (k) * kCtrStride)
+constexpr const char* kGeomCapMessage =
+    "a TorusGeometry or ConicalShellGeometry found no position in 65536 attempts";
 constexpr int kSersicTable = 202;  // SersicFunction: 101 radii, then 101 cumulative masses
 constexpr int kDetectCopies = 8;   // most LDS copies of the SED sums in the detect kernel (one per 8 lanes)
 constexpr int kPollEvery = 1;      // iterations between two counter copies of a half
@@ -131,7 +134,11 @@ struct PathRec {
 };
 constexpr int kPathCap = 2048;
 constexpr int kContSlots = 1 << 15;  // packet slots in flight with continuous scattering (ray queue sizing)
-enum ErrorBits : unsigned { ERR_TAU = 1u, ERR_PATH_CAP = 2u, ERR_QUEUE = 4u };
+enum ErrorBits : unsigned { ERR_TAU = 1u, ERR_PATH_CAP = 2u, ERR_QUEUE = 4u, ERR_GEOM = 8u };
+static_assert(GEOMS_SHELL == SKIRT_GEOM_SHELL && GEOMS_GAMMA == SKIRT_GEOM_GAMMA && GEOMS_GAUSSIAN == SKIRT_GEOM_GAUSSIAN &&
+                  GEOMS_TTAURIDISK == SKIRT_GEOM_TTAURIDISK && GEOMS_TORUS == SKIRT_GEOM_TORUS &&
+                  GEOMS_CONICALSHELL == SKIRT_GEOM_CONICALSHELL,
+              "geom_sample.hpp follows the kinds of skirt_mcrt.h");
 template <int GRID>
 constexpr bool kEnterInEvent = GRID == SKIRT_GRID_VORONOI;
 // Voronoi cellIndex: block-list candidates loaded per round trip. Round 3 chose 4; with the round-4
@@ -2487,8 +2494,8 @@ struct Events {
 
     // ExpDiskGeometry::randomR / randomz and SepAxGeometry::generatePosition (R, phi = 2 pi u, z;
     // Position(R, phi, z, CYLINDRICAL)); gp = {hR, hz, Rmax, zmax, Rmin, rho0, 0, kind}
-    __device__ __forceinline__ void expDiskPosition(PacketRng& rng, const double* gp, double& x, double& y,
-                                                    double& z) const {
+    __device__ __forceinline__ static void expDiskPosition(PacketRng& rng, const double* gp, double& x, double& y,
+                                                           double& z) {
         const double hR = gp[0], hz = gp[1], Rmax = gp[2], zmax = gp[3], Rmin = gp[4];
         double R, X;
         do {
@@ -2510,7 +2517,7 @@ struct Events {
     // cos(theta) = 2u-1, sin(theta) = sqrt(1-cos^2) and sin/cos(2 pi u') = sinpi/cospi(2u') -- the
     // same values to rounding, without acos or a large-argument reduction. The reference's 1e-8
     // pole cut-offs in Direction(theta, phi) are never reached by a deviate in (0,1).
-    __device__ __forceinline__ void isotropic(PacketRng& rng, double& x, double& y, double& z) const {
+    __device__ __forceinline__ static void isotropic(PacketRng& rng, double& x, double& y, double& z) {
         const double ct = 2.0 * rng.uniform() - 1.0;
         const double u = rng.uniform();
         const double st = sqrt((1.0 - ct) * (1.0 + ct));
@@ -2675,6 +2682,52 @@ struct Events {
         }
     }
 
+    // Geometry::generatePosition of source component h (gp: its row of the device geometry table, the kind in
+    // its eighth word), shared by launchStellar and skirt_mcrt_sample_positions
+    __device__ __forceinline__ static bool launchPosition(const double* gp, const double* geomTable, int h,
+                                                          PacketRng& rng, double& x, double& y, double& z) {
+        // the six closed-form kinds (geom_sample.hpp), the torus and the cone (the rest of whose constants start
+        // their geom_table row) apart from the other four: dispatched this way every event kernel keeps its three
+        // waves per SIMD (profiles/geom_first.txt). False when a rejection loop reached its cap.
+        if ((int)gp[7] >= SKIRT_GEOM_TORUS) {
+            return geomConePosition(gp, geomTable + (size_t)kSersicTable * h, rng, x, y, z);
+        } else if ((int)gp[7] >= SKIRT_GEOM_SHELL) {
+            return geomPositionOf((int)gp[7], gp, nullptr, rng, x, y, z);
+        } else if ((int)gp[7] == SKIRT_GEOM_POINT) {
+            x = 0.0; y = 0.0; z = 0.0;  // PointGeometry::generatePosition: no draws
+        } else if ((int)gp[7] == SKIRT_GEOM_EXPDISK) {
+            expDiskPosition(rng, gp, x, y, z);
+        } else if ((int)gp[7] == SKIRT_GEOM_SERSIC) {
+            // SersicGeometry::randomradius (SersicFunction::inversemass: locate_clip + log-log
+            // interpolation of the cumulative mass table) and SpheGeometry::generatePosition
+            const double* sv = geomTable + (size_t)kSersicTable * h;
+            const double* Mv = sv + kSersicTable / 2;
+            constexpr int Ns = kSersicTable / 2;
+            const double M = rng.uniform();
+            double sr;
+            if (M <= Mv[0]) sr = sv[0];
+            else if (M >= Mv[Ns - 1]) sr = sv[Ns - 1];
+            else {
+                int jl = -1, ju = Ns - 1;  // NR::locate_clip
+                while (ju - jl > 1) { const int jm = (ju + jl) >> 1; if (M < Mv[jm]) ju = jm; else jl = jm; }
+                sr = interpolateLogLog(M, Mv[jl], Mv[jl + 1], sv[jl], sv[jl + 1]);
+            }
+            const double rr = gp[0] * sr;
+            double ux, uy, uz;
+            isotropic(rng, ux, uy, uz);
+            x = rr * ux; y = rr * uy; z = rr * uz;
+        } else {
+            // PlummerGeometry::randomradius (t = u^(1/3)) and SpheGeometry::generatePosition
+            const double c = gp[0];
+            const double t = cbrt(rng.uniform());
+            const double rr = c * t / sqrt((1.0 - t) * (1.0 + t));
+            double ux, uy, uz;
+            isotropic(rng, ux, uy, uz);
+            x = rr * ux; y = rr * uy; z = rr * uz;
+        }
+        return true;
+    }
+
     // StellarSystem::launch + GeometricStellarComp::launch + PlummerGeometry sampling (see below)
     __device__ __forceinline__ bool launchStellar(Packet& p, unsigned long long idx) {
         const int ell = (int)(idx / a.npp);
@@ -2705,38 +2758,9 @@ struct Events {
             const double Lmean = a.lumtot[ell] / N;
             L = L0 * (1.0 / (1.0 - xi + xi * Lmean / Lh));
         }
-        const double* gp = a.geomParam + 8 * h;
-        if ((int)gp[7] == SKIRT_GEOM_POINT) {
-            p.rx = 0.0; p.ry = 0.0; p.rz = 0.0;  // PointGeometry::generatePosition: no draws
-        } else if ((int)gp[7] == SKIRT_GEOM_EXPDISK) {
-            expDiskPosition(p.rng, gp, p.rx, p.ry, p.rz);
-        } else if ((int)gp[7] == SKIRT_GEOM_SERSIC) {
-            // SersicGeometry::randomradius (SersicFunction::inversemass: locate_clip + log-log
-            // interpolation of the cumulative mass table) and SpheGeometry::generatePosition
-            const double* sv = a.geomTable + (size_t)kSersicTable * h;
-            const double* Mv = sv + kSersicTable / 2;
-            constexpr int Ns = kSersicTable / 2;
-            const double M = p.rng.uniform();
-            double sr;
-            if (M <= Mv[0]) sr = sv[0];
-            else if (M >= Mv[Ns - 1]) sr = sv[Ns - 1];
-            else {
-                int jl = -1, ju = Ns - 1;  // NR::locate_clip
-                while (ju - jl > 1) { const int jm = (ju + jl) >> 1; if (M < Mv[jm]) ju = jm; else jl = jm; }
-                sr = interpolateLogLog(M, Mv[jl], Mv[jl + 1], sv[jl], sv[jl + 1]);
-            }
-            const double rr = gp[0] * sr;
-            double ux, uy, uz;
-            isotropic(p.rng, ux, uy, uz);
-            p.rx = rr * ux; p.ry = rr * uy; p.rz = rr * uz;
-        } else {
-            // PlummerGeometry::randomradius (t = u^(1/3)) and SpheGeometry::generatePosition
-            const double c = gp[0];
-            const double t = cbrt(p.rng.uniform());
-            const double rr = c * t / sqrt((1.0 - t) * (1.0 + t));
-            double ux, uy, uz;
-            isotropic(p.rng, ux, uy, uz);
-            p.rx = rr * ux; p.ry = rr * uy; p.rz = rr * uz;
+        if (!launchPosition(a.geomParam + 8 * h, a.geomTable, h, p.rng, p.rx, p.ry, p.rz)) {
+            atomicOr(a.error, ERR_GEOM);  // a torus or cone whose rejection loop reached its cap: SKIRT_ERR_NUMERIC
+            return false;
         }
         // the emission direction Random::direction()
         isotropic(p.rng, p.kx, p.ky, p.kz);
@@ -3614,9 +3638,27 @@ __device__ double geomDensity(const DensArgs& d, int h, double x, double y, doub
         if (logf) fx = pow(10.0, fx);
         return p[2] * fx;
     }
-    default:  // SKIRT_GEOM_POINT
+    case SKIRT_GEOM_POINT:
         return (x * x + y * y + z * z) == 0 ? INFINITY : 0.0;
+    default:  // the six closed-form kinds (geom_sample.hpp)
+        return geomDensityOf(d.kind[h], p, d.table ? d.table + (size_t)2 * d.ntab * h : nullptr, x, y, z);
     }
+}
+
+// Geometry::generatePosition of one source component on fresh per-packet streams (skirt_mcrt_sample_positions):
+// the routines Events::launchStellar runs, one packet per thread
+__global__ void __launch_bounds__(kBlock)
+    samplePositionsKernel(const double* geomParam, const double* geomTable, int h, unsigned long long seed,
+                          unsigned long long first, size_t n, double* pos, int* draws, unsigned* error) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    PacketRng rng;
+    rng.start(seed, SKIRT_POSITIONS_TAG, first + i);
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (!Events<SKIRT_GRID_CARTESIAN, true>::launchPosition(geomParam + 8 * h, geomTable, h, rng, x, y, z))
+        atomicOr(error, ERR_GEOM);
+    pos[3 * i] = x; pos[3 * i + 1] = y; pos[3 * i + 2] = z;
+    draws[i] = (int)(2u * rng.block - (rng.have ? 1u : 0u));
 }
 
 __global__ void __launch_bounds__(kBlock) densitySampleKernel(const DensArgs d) {
@@ -4089,11 +4131,14 @@ int skirt_mcrt_upload_sources(SkirtMcrt* c, const SkirtSourceDesc* s) {
     std::vector<double> gp(8 * (size_t)s->ncomp);
     bool tables = false;
     for (int h = 0; h < s->ncomp; h++) {
-        if (s->geom_kind[h] != SKIRT_GEOM_PLUMMER && s->geom_kind[h] != SKIRT_GEOM_EXPDISK &&
-            s->geom_kind[h] != SKIRT_GEOM_SERSIC && s->geom_kind[h] != SKIRT_GEOM_POINT)
+        if (s->geom_kind[h] < SKIRT_GEOM_PLUMMER || s->geom_kind[h] > SKIRT_GEOM_CONICALSHELL)
             return fail(c, SKIRT_ERR_UNSUPPORTED, "unsupported source geometry");
         if (s->geom_kind[h] == SKIRT_GEOM_SERSIC) {
             if (!s->geom_table) return fail(c, SKIRT_ERR_ARG, "SersicGeometry without its tables");
+            tables = true;
+        }
+        if (s->geom_kind[h] == SKIRT_GEOM_TORUS || s->geom_kind[h] == SKIRT_GEOM_CONICALSHELL) {
+            if (!s->geom_table) return fail(c, SKIRT_ERR_ARG, "TorusGeometry or ConicalShellGeometry without its table row");
             tables = true;
         }
         for (int q = 0; q < 7; q++) gp[8 * h + q] = s->geom_param[8 * h + q];
@@ -4942,6 +4987,7 @@ int skirt_mcrt_synchronize(SkirtMcrt* c) {
     unsigned int e = 0;
     HIPCHECK(c, hipMemcpy(&e, c->dError, sizeof e, hipMemcpyDeviceToHost));
     if (e & ERR_TAU) return fail(c, SKIRT_ERR_NUMERIC, "the optical depth along the path is not a positive number");
+    if (e & ERR_GEOM) return fail(c, SKIRT_ERR_NUMERIC, kGeomCapMessage);
     if (e & ERR_PATH_CAP)
         return fail(c, SKIRT_ERR_UNSUPPORTED, "continuous scattering: a path crosses more than " +
                                                   std::to_string(kPathCap) + " dust cells");
@@ -5130,6 +5176,42 @@ void skirt_mcrt_destroy(SkirtMcrt* c) {
     delete c;
 }
 
+int skirt_mcrt_sample_positions(SkirtMcrt* c, int comp, uint64_t seed, uint64_t first, size_t n, double* pos,
+                                int32_t* draws) {
+    if (!c) return SKIRT_ERR_ARG;
+    if (!c->dGeomParam || c->nstar < 1) return fail(c, SKIRT_ERR_STATE, "sample_positions before upload_sources");
+    if (comp < 0 || comp >= c->nstar || (n && !pos)) return fail(c, SKIRT_ERR_ARG, "bad component or buffer");
+    if (n == 0) return SKIRT_OK;
+    const size_t nblocks = (n + kBlock - 1) / kBlock;
+    if (nblocks > 0x7fffffffu) return fail(c, SKIRT_ERR_ARG, "too many positions");
+    HIPCHECK(c, hipSetDevice(c->device));
+    double* dPos = nullptr;
+    int* dDraws = nullptr;
+    unsigned* dErr = nullptr;
+    unsigned err = 0;
+    int rc = SKIRT_OK;
+    if (hipMalloc(&dPos, 3 * n * sizeof(double)) != hipSuccess || hipMalloc(&dDraws, n * sizeof(int)) != hipSuccess ||
+        hipMalloc(&dErr, sizeof(unsigned)) != hipSuccess ||
+        hipMemsetAsync(dErr, 0, sizeof(unsigned), c->stream) != hipSuccess) {
+        rc = fail(c, SKIRT_ERR_HIP, "sample_positions: allocation failed");
+    } else {
+        hipLaunchKernelGGL(samplePositionsKernel, dim3((unsigned)nblocks), dim3(kBlock), 0, c->stream, c->dGeomParam,
+                           c->dGeomTable, comp, (unsigned long long)seed, (unsigned long long)first, n, dPos, dDraws, dErr);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(pos, dPos, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            (draws && hipMemcpyAsync(draws, dDraws, n * sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+            hipMemcpyAsync(&err, dErr, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess)
+            rc = fail(c, SKIRT_ERR_HIP, "sample_positions: the kernel or a copy failed");
+        else if (err & ERR_GEOM)
+            rc = fail(c, SKIRT_ERR_NUMERIC, kGeomCapMessage);
+    }
+    if (dPos) (void)hipFree(dPos);
+    if (dDraws) (void)hipFree(dDraws);
+    if (dErr) (void)hipFree(dErr);
+    return rc;
+}
+
 int skirt_mcrt_sample_density(int device, const SkirtDensityDesc* dens, const double* boxes, size_t n,
                               const uint32_t* words, int nsample, int mode, double* out) {
     if (!dens || dens->ncomp < 1 || !dens->geom_kind || !dens->geom_param || !dens->norm || nsample < 1 ||
@@ -5137,8 +5219,10 @@ int skirt_mcrt_sample_density(int device, const SkirtDensityDesc* dens, const do
         return SKIRT_ERR_ARG;
     for (int h = 0; h < dens->ncomp; h++) {
         const int k = dens->geom_kind[h];
-        if (k < SKIRT_GEOM_PLUMMER || k > SKIRT_GEOM_POINT) return SKIRT_ERR_ARG;
-        if (k == SKIRT_GEOM_SERSIC && (!dens->dens_table || dens->ntab < 2)) return SKIRT_ERR_ARG;
+        if (k < SKIRT_GEOM_PLUMMER || k > SKIRT_GEOM_CONICALSHELL) return SKIRT_ERR_ARG;
+        if ((k == SKIRT_GEOM_SERSIC || k == SKIRT_GEOM_TORUS || k == SKIRT_GEOM_CONICALSHELL) &&
+            (!dens->dens_table || dens->ntab < 2))
+            return SKIRT_ERR_ARG;
     }
     if (n == 0) return SKIRT_OK;
     const size_t nout = n * (mode == SKIRT_DENS_NODE ? 6 : (size_t)dens->ncomp);

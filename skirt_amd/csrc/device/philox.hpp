@@ -36,7 +36,9 @@ struct PacketRng {
 
     __host__ __device__ static inline void philox(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3,
                                                   uint32_t key0, uint32_t key1) {
+#if defined(__clang__)  // the host driver includes this header too (g++)
 #pragma unroll
+#endif
         for (int r = 0; r < 10; r++) {
             const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
             const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;

@@ -183,6 +183,29 @@ static double sum(const std::vector<double>& v) { return std::accumulate(v.begin
 
 // ============================================================ model member functions
 
+// SpecialFunctions::gln / gln2 / gexp (SpecialFunctions.cpp:754-791)
+double gln(double p, double x) {
+    const double q = 1.0 - p;
+    if (q == 0.0) return std::log(x);
+    else if (std::fabs(q) < 1e-3) {
+        const double lnx = std::log(x);
+        const double s = q * lnx;
+        return lnx * (1.0 + 0.5 * s + 1.0 / 6.0 * s * s + 1.0 / 24.0 * s * s * s);
+    } else
+        return (std::pow(x, q) - 1.0) / q;
+}
+double gln2(double p, double x1, double x2) { return std::pow(x2, 1.0 - p) * gln(p, x1 / x2); }
+double gexp(double p, double x) {
+    const double q = 1.0 - p;
+    if (q == 0.0) return std::exp(x);
+    else if (std::fabs(q) < 1e-3) {
+        const double x2 = x * x;
+        return std::exp(x) * (1.0 - 0.5 * x2 * q + 1.0 / 24.0 * x * x2 * (8.0 + 3.0 * x) * q * q -
+                              1.0 / 48.0 * x2 * x2 * (12.0 + 8.0 * x + x2) * q * q * q);
+    } else
+        return std::pow(1.0 + q * x, 1.0 / q);
+}
+
 double Geometry::density(double x, double y, double z) const {
     switch (kind) {
     case GeometryKind::Plummer: {
@@ -211,16 +234,59 @@ double Geometry::density(double x, double y, double z) const {
         else if (R < Rmin) return 0.0;
         return rho0 * std::exp(-R / hR) * std::exp(-absz / hz);
     }
+    case GeometryKind::Shell: {  // ShellGeometry::density(r)
+        const double r = std::sqrt(x * x + y * y + z * z);
+        if (r < rmin || r > rmax) return 0.0;
+        return A * std::pow(r, -p);
+    }
+    case GeometryKind::Gamma: {  // GammaGeometry::density(r)
+        const double r = std::sqrt(x * x + y * y + z * z);
+        return rho0 * std::pow(r / b, -gamma) * std::pow(1.0 + r / b, gamma - 4.0);
+    }
+    case GeometryKind::Gaussian: {  // GaussianGeometry::density(R, z)
+        const double R = std::sqrt(x * x + y * y);
+        const double m2 = R * R + z * z / (q * q);
+        const double sigma2 = sigma * sigma;
+        return rho0 * std::exp(-0.5 * m2 / sigma2);
+    }
+    case GeometryKind::TTauriDisk: {  // TTauriDiskGeometry::density(R, z)
+        const double R = std::sqrt(x * x + y * y);
+        if (R < rmin || R > rmax) return 0.0;
+        const double h = zd * std::pow(R / Rd, 1.125);
+        return rho0 / (R / Rd) * std::exp(-M_PI / 4.0 * std::pow(z / h, 2));
+    }
+    case GeometryKind::Torus:
+    case GeometryKind::ConicalShell: {  // TorusGeometry::density(R, z), ConicalShellGeometry::density(R, z)
+        const double R = std::sqrt(x * x + y * y);
+        const double r = std::sqrt(R * R + z * z);
+        const double costheta = z / r;
+        if (r >= rmax) return 0.0;
+        if (rani) {
+            const double rminani = rmin * std::sqrt(6. / 7. * std::fabs(costheta) * (2. * std::fabs(costheta) + 1));
+            if (r <= rminani || r < rcut) return 0.0;
+        } else {
+            if (r <= rmin) return 0.0;
+        }
+        if (std::fabs(costheta) >= sinDelta) return 0.0;
+        if (kind == GeometryKind::ConicalShell && std::fabs(costheta) <= sinDeltaIn) return 0.0;
+        return A * std::pow(r, -p) * std::exp(-q * std::fabs(costheta));
+    }
     }
     return 0;
 }
 
 double Geometry::SigmaR() const {
+    if (kind == GeometryKind::Gaussian) return 1.0 / (4.0 * M_PI * q * sigma * sigma);
+    if (kind == GeometryKind::TTauriDisk) return rho0 * Rd * std::log(rmax / rmin);
+    if (kind == GeometryKind::Torus) return A * gln2(p, rmax, rmin);
+    if (kind == GeometryKind::ConicalShell) return A * std::exp(-q * cosDelta) * gln2(p, rmax, rmin);
     if (kind != GeometryKind::ExpDisk) throw std::runtime_error("Geometry is not axisymmetric");
     if (Rmax > 0.0) return rho0 * hR * (std::exp(-Rmin / hR) - std::exp(-Rmax / hR));
     return rho0 * hR * std::exp(-Rmin / hR);
 }
 double Geometry::SigmaZ() const {
+    if (kind == GeometryKind::Gaussian) return 1.0 / (2.0 * M_PI * sigma * sigma);
+    if (kind == GeometryKind::TTauriDisk || kind == GeometryKind::Torus || kind == GeometryKind::ConicalShell) return 0.0;
     if (kind != GeometryKind::ExpDisk) throw std::runtime_error("Geometry is not axisymmetric");
     if (Rmin > 0.0) return 0.0;
     if (zmax > 0.0) return -2.0 * rho0 * hz * std::expm1(-zmax / hz);
@@ -229,6 +295,10 @@ double Geometry::SigmaZ() const {
 static double lngamma(double a);
 double Geometry::Sigmar() const {
     if (kind == GeometryKind::Plummer) return 0.5 / (M_PI * c * c);
+    if (kind == GeometryKind::Shell) return A * gln2(p, rmax, rmin);
+    if (kind == GeometryKind::Gamma)
+        return gamma < 1.0 ? 1.0 / (2.0 * M_PI * b * b * (1.0 - gamma) * (2.0 - gamma))
+                           : std::numeric_limits<double>::infinity();
     if (kind == GeometryKind::Sersic)
         return 1.0 / (reff * reff) * std::pow(b, 2.0 * n) / (2.0 * M_PI * std::exp(lngamma(2.0 * n + 1.0)));
     throw std::runtime_error("Geometry is not spherically symmetric");
@@ -571,6 +641,39 @@ const XmlElement* need(const XmlElement* e, const char* prop) {
     return it;
 }
 
+// The rejection loops of TorusGeometry and ConicalShellGeometry::generatePosition have no bound in the reference;
+// parameters that admit no position (an anisotropic inner radius with cutRadius >= maxRadius, say) make it spin.
+// The engine's loops end at kGeomAttemptCap attempts; a geometry whose acceptance, estimated here over 20000
+// attempts on a private stream (never the setup's generator, whose draw order is the reference's), is below 1e-3
+// is refused at load, so that the cap is out of reach (e^-65) for every model that loads.
+struct AcceptanceRng {
+    uint64_t s = 0x9E3779B97F4A7C15ull;
+    double uniform() {  // splitmix64, 53 bits, inside (0,1)
+        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        return ((double)(z >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    }
+};
+struct CountingRng {
+    AcceptanceRng r;
+    long draws = 0;
+    double uniform() { draws++; return r.uniform(); }
+};
+void checkAcceptance(const Geometry& geo, const std::string& name) {
+    const long attempts = 20000;
+    CountingRng rng;
+    long accepted = 0;
+    double x, y, z;
+    // three deviates per attempt: positions until the attempts are spent (a position that meets the cap ends it)
+    while (rng.draws < 3 * attempts && torusPosition(geo, rng, x, y, z)) accepted++;
+    if ((double)accepted < 1e-3 * (double)(rng.draws / 3))
+        throw std::runtime_error(name + ": fewer than 1 in 1000 candidate positions lie inside the geometry (" +
+                                 std::to_string(accepted) + " of " + std::to_string(rng.draws / 3) +
+                                 "); its parameters leave (almost) no volume");
+}
+
 Geometry parseGeometry(const Ctx& c, const XmlElement* g) {
     Geometry geo;
     if (g->name == "PlummerGeometry") {
@@ -610,6 +713,95 @@ Geometry parseGeometry(const Ctx& c, const XmlElement* g) {
         const double tmax = (geo.Rmax > 0) ? std::exp(-geo.Rmax / geo.hR) * (1.0 + geo.Rmax / geo.hR) : 0.0;
         const double intR = geo.hR * geo.hR * (tmin - tmax);
         geo.rho0 = 1.0 / (intR * intphi * intz);
+    } else if (g->name == "ShellGeometry") {
+        // ShellGeometry::setupSelfBefore
+        geo.kind = GeometryKind::Shell;
+        geo.rmin = attr(c, g, "minRadius", "length", 0);
+        geo.rmax = attr(c, g, "maxRadius", "length", 0);
+        geo.p = attr(c, g, "expon", "", 0);
+        if (geo.rmin <= 0) throw std::runtime_error("the inner radius of the shell should be positive");
+        if (geo.rmax <= geo.rmin)
+            throw std::runtime_error("the outer radius of the shell should be larger than the inner radius");
+        if (geo.p < 0) throw std::runtime_error("the power law exponent p should be positive");
+        geo.smin = gln(geo.p - 2.0, geo.rmin);
+        geo.sdiff = gln2(geo.p - 2.0, geo.rmax, geo.rmin);
+        geo.A = 0.25 / M_PI / geo.sdiff;
+    } else if (g->name == "GammaGeometry") {
+        // GammaGeometry::setupSelfBefore
+        geo.kind = GeometryKind::Gamma;
+        geo.b = attr(c, g, "scale", "length", 0);
+        geo.gamma = attr(c, g, "gamma", "", 1);
+        if (geo.b <= 0) throw std::runtime_error("the scale length b should be positive");
+        if (geo.gamma < 0 || geo.gamma >= 3.0)
+            throw std::runtime_error("the central density slope gamma should be between 0 and 3");
+        geo.rho0 = (3.0 - geo.gamma) / (4.0 * M_PI) / std::pow(geo.b, 3);
+    } else if (g->name == "GaussianGeometry") {
+        // GaussianGeometry::setupSelfBefore
+        geo.kind = GeometryKind::Gaussian;
+        geo.sigma = attr(c, g, "dispersion", "length", 0);
+        geo.q = attr(c, g, "flattening", "", 0);
+        if (geo.sigma <= 0) throw std::runtime_error("the dispersion parameter sigma should be positive");
+        if (geo.q <= 0 || geo.q > 1.0) throw std::runtime_error("the flattening parameter q should be between 0 and 1");
+        geo.rho0 = 1.0 / std::pow(std::sqrt(2.0 * M_PI) * geo.sigma, 3) / geo.q;
+    } else if (g->name == "TTauriDiskGeometry") {
+        // TTauriDiskGeometry::setupSelfBefore
+        geo.kind = GeometryKind::TTauriDisk;
+        geo.rmin = attr(c, g, "minRadius", "length", 0);
+        geo.rmax = attr(c, g, "maxRadius", "length", 0);
+        geo.Rd = attr(c, g, "radialScale", "length", 0);
+        geo.zd = attr(c, g, "axialScale", "length", 0);
+        if (geo.rmin <= 0) throw std::runtime_error("the inner radius of the disk should be positive");
+        if (geo.rmax <= geo.rmin)
+            throw std::runtime_error("the outer radius of the disk must be larger than the inner radius");
+        if (geo.Rd <= 0) throw std::runtime_error("the radial scale length Rd should be positive");
+        if (geo.zd <= 0) throw std::runtime_error("the axial scale height zd should be positive");
+        geo.rho0 = 17.0 / 32.0 / M_PI / (geo.Rd * geo.Rd * geo.zd) /
+                   (std::pow(geo.rmax / geo.Rd, 17.0 / 8.0) - std::pow(geo.rmin / geo.Rd, 17.0 / 8.0));
+    } else if (g->name == "TorusGeometry" || g->name == "ConicalShellGeometry") {
+        // TorusGeometry::setupSelfBefore (its RotateGeometryDecorator look-up finds none: _beta = 0) and
+        // ConicalShellGeometry::setupSelfBefore
+        const bool cone = g->name == "ConicalShellGeometry";
+        const std::string of = cone ? " of the conical shell" : " of the torus";
+        geo.kind = cone ? GeometryKind::ConicalShell : GeometryKind::Torus;
+        geo.p = attr(c, g, "expon", "", 0);
+        geo.q = attr(c, g, "index", "", 0);
+        geo.Delta = attr(c, g, cone ? "outAngle" : "openAngle", "posangle", 0);
+        geo.DeltaIn = cone ? attr(c, g, "inAngle", "posangle", 0) : 0.0;
+        geo.rmin = attr(c, g, "minRadius", "length", 0);
+        geo.rmax = attr(c, g, "maxRadius", "length", 0);
+        geo.rani = attrBool(g, "anisoRadius", false);
+        geo.rcut = attr(c, g, "cutRadius", "length", 0);
+        if (geo.p < 0) throw std::runtime_error("The radial power law exponent p" + of + " should be positive");
+        if (geo.q < 0) throw std::runtime_error("The polar index q" + of + " should be positive");
+        if (cone) {
+            if (geo.DeltaIn < 0) throw std::runtime_error("The inner angle of the conical shell should be positive");
+            if (geo.Delta < 0) throw std::runtime_error("The outer angle of the conical shell should be positive");
+            if (geo.Delta <= geo.DeltaIn)
+                throw std::runtime_error("the outer angle of the shell should be larger than the inner angle");
+        } else if (geo.Delta < 0) {
+            throw std::runtime_error("The half opening angle of the torus should be positive");
+        }
+        if (geo.rmin <= 0) throw std::runtime_error("The minimum radius" + of + " should be positive");
+        if (geo.rmax <= geo.rmin)
+            throw std::runtime_error("The maximum radius" + of + " should be larger than the minimum radius");
+        if (geo.rani && geo.rcut <= 0) throw std::runtime_error("The inner cutoff radius of the torus should be positive");
+        geo.sinDelta = std::sin(geo.Delta);
+        geo.smin = gln(geo.p - 2.0, geo.rmin);
+        geo.sdiff = gln2(geo.p - 2.0, geo.rmax, geo.rmin);
+        if (cone) {
+            geo.sinDeltaIn = std::sin(geo.DeltaIn);
+            geo.cosDelta = std::cos((geo.Delta + geo.DeltaIn) / 2.);
+            if (geo.q > 1e-3)
+                geo.A = geo.q * 0.25 / M_PI / geo.sdiff /
+                        (std::exp(-geo.q * geo.sinDeltaIn) - std::exp(-geo.q * geo.sinDelta));
+            else
+                geo.A = 0.25 / M_PI / geo.sdiff / (geo.sinDelta - geo.sinDeltaIn);
+        } else {
+            geo.sinDeltaIn = -1.0;  // no inner angle: no |cos theta| lies at or below it
+            if (geo.q > 1e-3) geo.A = geo.q * 0.25 / M_PI / geo.sdiff / (1.0 - std::exp(-geo.q * geo.sinDelta));
+            else geo.A = 0.25 / M_PI / geo.sdiff / geo.sinDelta;
+        }
+        checkAcceptance(geo, g->name);
     } else {
         throw std::runtime_error("unsupported geometry " + g->name);
     }
@@ -1359,29 +1551,10 @@ static void buildVoronoiGrid(const Ctx& c, const XmlElement* ge, Model& m, Unifo
                 if (X < cum[0]) h = 0;
                 else h = nr::locateBasic(cum, X, (int)cum.size() - 1);
                 const Geometry& geo = m.dust[h].geom;
-                if (geo.kind != GeometryKind::Plummer) {
-                    double x, y, z;
-                    if (geo.kind == GeometryKind::ExpDisk) expDiskPosition(geo, rng, x, y, z);
-                    else sersicPosition(geo, rng, x, y, z);
-                    if (contains(x, y, z)) {
-                        sites[3 * q] = x; sites[3 * q + 1] = y; sites[3 * q + 2] = z;
-                        break;
-                    }
-                    continue;
-                }
-                // PlummerGeometry::randomradius, then SpheGeometry::generatePosition (Random::direction)
-                double t = std::pow(rng.uniform(), 1.0 / 3.0);
-                double r = geo.c * t / std::sqrt((1.0 - t) * (1.0 + t));
-                double theta = std::acos(2.0 * rng.uniform() - 1.0);
-                double phi = 2.0 * M_PI * rng.uniform();
-                double kx, ky, kz;
-                if (theta <= 1e-8) { kx = 0; ky = 0; kz = 1; }  // Direction(theta, phi), Direction.cpp
-                else if (theta >= M_PI - 1e-8) { kx = 0; ky = 0; kz = -1; }
-                else {
-                    double st = std::sin(theta);
-                    kx = st * std::cos(phi); ky = st * std::sin(phi); kz = std::cos(theta);
-                }
-                double x = r * kx, y = r * ky, z = r * kz;
+                // Geometry::generatePosition of the component's kind, in the reference's draw order
+                double x, y, z;
+                if (!geometryPosition(geo, rng, x, y, z))
+                    throw std::runtime_error("a TorusGeometry or ConicalShellGeometry found no position in 65536 attempts");
                 if (contains(x, y, z)) {
                     sites[3 * q] = x; sites[3 * q + 1] = y; sites[3 * q + 2] = z;
                     break;

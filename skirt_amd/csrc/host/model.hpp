@@ -27,15 +27,36 @@ namespace skirt {
 // tables of the deprojected profile S(s) and the cumulative mass M(s), log-log interpolated) and
 // SpheGeometry::generatePosition (radius, then Random::direction).
 // PointGeometry.cpp: every position at the origin (no random draws), an infinite density there.
-enum class GeometryKind : int { Plummer = 0, ExpDisk = 1, Sersic = 2, Point = 3 };
+// ShellGeometry.cpp, GammaGeometry.cpp (SpheGeometry: randomradius, then Random::direction), GaussianGeometry.cpp
+// (SepAxGeometry: R, phi, z), TTauriDiskGeometry.cpp and TorusGeometry.cpp, ConicalShellGeometry.cpp (AxGeometry with
+// a generatePosition of their own; the last two reject positions by their density), with SpecialFunctions::gln /
+// gln2 / gexp and Random::gauss. A TorusGeometry's RotateGeometryDecorator look-up does not apply (no decorators).
+enum class GeometryKind : int {
+    Plummer = 0, ExpDisk = 1, Sersic = 2, Point = 3, Shell = 4, Gamma = 5, Gaussian = 6, TTauriDisk = 7, Torus = 8,
+    ConicalShell = 9
+};
+
+// SpecialFunctions::gln, gln2, gexp (SpecialFunctions.cpp:754-791)
+double gln(double p, double x);
+double gln2(double p, double x1, double x2);
+double gexp(double p, double x);
 
 struct Geometry {
     GeometryKind kind = GeometryKind::Plummer;
     double c = 0;     // Plummer scale length
     double rho0 = 0;  // Plummer: 0.75/c^3/pi (PlummerGeometry.cpp setupSelfBefore); ExpDisk, Sersic: theirs
     double hR = 0, hz = 0, Rmax = 0, zmax = 0, Rmin = 0;  // ExpDisk scales and truncations (0: none)
-    double n = 0, reff = 0, b = 0;             // Sersic index, effective radius and b(n)
+    double n = 0, reff = 0, b = 0;             // Sersic index, effective radius and b(n); Gamma: its scale length b
     std::vector<double> sv, Sv, Mv;            // SersicFunction tables
+    // Shell, Torus, ConicalShell: radial range, exponent p, cached smin, sdiff and normalization A.
+    // Torus, ConicalShell: polar index q, (outer) half opening angle Delta and inner angle DeltaIn with their sines,
+    // cos of the mean angle, anisotropic inner radius (rani) and its cutoff rcut
+    double rmin = 0, rmax = 0, p = 0, smin = 0, sdiff = 0, A = 0;
+    double q = 0, Delta = 0, DeltaIn = 0, sinDelta = 0, sinDeltaIn = 0, cosDelta = 0, rcut = 0;
+    bool rani = false;
+    // Gamma: slope gamma (scale in b); Gaussian: dispersion sigma (flattening in q); TTauriDisk: radial scale Rd and
+    // axial scale zd (inner and outer radius in rmin, rmax); rho0 above for the three
+    double gamma = 0, sigma = 0, Rd = 0, zd = 0;
 
     double density(double x, double y, double z) const;
     double sersicInverseMass(double M) const;  // SersicFunction::inversemass
@@ -83,6 +104,131 @@ void sersicPosition(const Geometry& g, R& rng, double& x, double& y, double& z) 
         kx = st * std::cos(phi); ky = st * std::sin(phi); kz = std::cos(theta);
     }
     x = r * kx; y = r * ky; z = r * kz;
+}
+
+// Random::gauss (Random.cpp:140-150)
+template <class R>
+double gaussDeviate(R& rng) {
+    double rsq, v1, v2;
+    do {
+        v1 = 2.0 * rng.uniform() - 1.0;
+        v2 = 2.0 * rng.uniform() - 1.0;
+        rsq = v1 * v1 + v2 * v2;
+    } while (rsq >= 1.0 || rsq == 0.0);
+    return v2 * std::sqrt(-2.0 * std::log(rsq) / rsq);
+}
+
+// SpheGeometry::generatePosition after randomradius: Position(r, Random::direction())
+template <class R>
+void radialPosition(double r, R& rng, double& x, double& y, double& z) {
+    const double theta = std::acos(2.0 * rng.uniform() - 1.0);
+    const double phi = 2.0 * M_PI * rng.uniform();
+    double kx, ky, kz;
+    if (theta <= 1e-8) { kx = 0; ky = 0; kz = 1; }
+    else if (theta >= M_PI - 1e-8) { kx = 0; ky = 0; kz = -1; }
+    else {
+        const double st = std::sin(theta);
+        kx = st * std::cos(phi); ky = st * std::sin(phi); kz = std::cos(theta);
+    }
+    x = r * kx; y = r * ky; z = r * kz;
+}
+
+// ShellGeometry::randomradius
+template <class R>
+void shellPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
+    const double X = rng.uniform();
+    const double s = g.smin + X * g.sdiff;
+    radialPosition(gexp(g.p - 2.0, s), rng, x, y, z);
+}
+
+// GammaGeometry::randomradius
+template <class R>
+void gammaPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
+    const double X = rng.uniform();
+    const double t = std::pow(X, 1.0 / (3.0 - g.gamma));
+    radialPosition(g.b * t / (1.0 - t), rng, x, y, z);
+}
+
+// GaussianGeometry::randomR / randomz in SepAxGeometry::generatePosition's order (R, phi, z)
+template <class R>
+void gaussianPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
+    const double X = rng.uniform();
+    const double Rc = g.sigma * std::sqrt(-2.0 * std::log(X));
+    const double phi = 2.0 * M_PI * rng.uniform();
+    z = (g.q * g.sigma) * gaussDeviate(rng);
+    x = Rc * std::cos(phi);
+    y = Rc * std::sin(phi);
+}
+
+// TTauriDiskGeometry::generatePosition (TTauriDiskGeometry.cpp:107-118): phi, R, z
+template <class R>
+void ttauriPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
+    const double phi = 2.0 * M_PI * rng.uniform();
+    const double tinn = std::pow(g.rmin, 2.125);
+    const double tout = std::pow(g.rmax, 2.125);
+    const double Rc = std::pow(tinn + rng.uniform() * (tout - tinn), 1.0 / 2.125);
+    const double h = g.zd * std::pow(Rc / g.Rd, 1.125);
+    const double sigma = std::sqrt(2.0 / M_PI) * h;
+    z = gaussDeviate(rng) * sigma;
+    x = Rc * std::cos(phi);
+    y = Rc * std::sin(phi);
+}
+
+// the rejection loops' cap (an engine choice; the reference's loops have none)
+constexpr int kGeomAttemptCap = 1 << 16;
+
+// TorusGeometry::generatePosition (:179-201) and ConicalShellGeometry::generatePosition (:190-212); false when
+// kGeomAttemptCap attempts were rejected
+template <class R>
+bool torusPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
+    for (int attempt = 0; attempt < kGeomAttemptCap; attempt++) {
+        double X = rng.uniform();
+        const double s = g.smin + X * g.sdiff;
+        const double r = gexp(g.p - 2.0, s);
+        X = rng.uniform();
+        double costheta = 0.0;
+        if (g.q < 1e-3) costheta = (1.0 - 2.0 * X) * g.sinDelta;
+        else {
+            const double B = 1.0 - std::exp(-g.q * g.sinDelta);
+            costheta = (X < 0.5) ? -std::log(1.0 - B * (1.0 - 2.0 * X)) / g.q
+                                 : std::log(1.0 - B * (2.0 * X - 1.0)) / g.q;
+        }
+        const double theta = std::acos(costheta);
+        X = rng.uniform();
+        const double phi = 2.0 * M_PI * X;
+        // Position(r, theta, phi, SPHERICAL), Position.cpp
+        const double ct = std::cos(theta), st = std::sin(theta), cp = std::cos(phi), sp = std::sin(phi);
+        const double px = r * st * cp, py = r * st * sp, pz = r * ct;
+        if (g.density(px, py, pz) != 0.0) {  // density(bfr.cylradius(), bfr.height())
+            x = px; y = py; z = pz;
+            return true;
+        }
+    }
+    x = y = z = 0.0;
+    return false;
+}
+
+// Geometry::generatePosition of every kind; false when a rejection loop reached its cap
+template <class R>
+bool geometryPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
+    switch (g.kind) {
+    case GeometryKind::ExpDisk: expDiskPosition(g, rng, x, y, z); return true;
+    case GeometryKind::Sersic: sersicPosition(g, rng, x, y, z); return true;
+    case GeometryKind::Point: x = y = z = 0.0; return true;
+    case GeometryKind::Shell: shellPosition(g, rng, x, y, z); return true;
+    case GeometryKind::Gamma: gammaPosition(g, rng, x, y, z); return true;
+    case GeometryKind::Gaussian: gaussianPosition(g, rng, x, y, z); return true;
+    case GeometryKind::TTauriDisk: ttauriPosition(g, rng, x, y, z); return true;
+    case GeometryKind::Torus:
+    case GeometryKind::ConicalShell: return torusPosition(g, rng, x, y, z);
+    case GeometryKind::Plummer: {
+        // PlummerGeometry::randomradius, then SpheGeometry::generatePosition (Random::direction)
+        const double t = std::pow(rng.uniform(), 1.0 / 3.0);
+        radialPosition(g.c * t / std::sqrt((1.0 - t) * (1.0 + t)), rng, x, y, z);
+        return true;
+    }
+    }
+    return true;
 }
 
 // ---------------------------------------------------------------- wavelength grid

@@ -361,7 +361,9 @@ void writeConvergence(const Model& m, const std::string& prefix, const double si
     int dim = 1;
     double ref[3] = {0, 0, 0}, Mref = 0;
     for (auto& d : m.dust) {
-        const bool ax = d.geom.kind == GeometryKind::ExpDisk;
+        const GeometryKind gk = d.geom.kind;  // AxGeometry (dimension 2) or SpheGeometry (dimension 1)
+        const bool ax = gk == GeometryKind::ExpDisk || gk == GeometryKind::Gaussian || gk == GeometryKind::TTauriDisk ||
+                        gk == GeometryKind::Torus || gk == GeometryKind::ConicalShell;
         dim = std::max(dim, ax ? 2 : 1);
         const double sxy = ax ? 2.0 * d.geom.SigmaR() : 2.0 * d.geom.Sigmar();
         ref[0] += d.nf * sxy;

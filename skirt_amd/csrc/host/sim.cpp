@@ -14,6 +14,7 @@
 #include "dustemission.hpp"
 #include "model.hpp"
 #include "outputs.hpp"
+#include "../device/philox.hpp"
 
 using namespace skirt;
 
@@ -93,9 +94,34 @@ int packGeometry(const Geometry& g, double* p) {
         for (int q = 0; q < 6; q++) p[q] = v[q];
         return SKIRT_GEOM_EXPDISK;
     }
+    case GeometryKind::Shell: {
+        const double v[6] = {g.rmin, g.rmax, g.p, g.smin, g.sdiff, g.A};
+        for (int q = 0; q < 6; q++) p[q] = v[q];
+        return SKIRT_GEOM_SHELL;
+    }
+    case GeometryKind::Gamma: p[0] = g.b; p[1] = g.gamma; p[2] = g.rho0; return SKIRT_GEOM_GAMMA;
+    case GeometryKind::Gaussian: p[0] = g.sigma; p[1] = g.q; p[2] = g.rho0; return SKIRT_GEOM_GAUSSIAN;
+    case GeometryKind::TTauriDisk: {
+        const double v[5] = {g.rmin, g.rmax, g.Rd, g.zd, g.rho0};
+        for (int q = 0; q < 5; q++) p[q] = v[q];
+        return SKIRT_GEOM_TTAURIDISK;
+    }
+    case GeometryKind::Torus:
+    case GeometryKind::ConicalShell: {
+        const double v[7] = {g.p, g.q, g.rmin, g.rmax, g.rani ? 1.0 : 0.0, g.rcut, g.A};
+        for (int q = 0; q < 7; q++) p[q] = v[q];
+        return g.kind == GeometryKind::Torus ? SKIRT_GEOM_TORUS : SKIRT_GEOM_CONICALSHELL;
+    }
     default: p[0] = g.c; p[1] = g.rho0; return SKIRT_GEOM_PLUMMER;
     }
 }
+// the first words of a TorusGeometry's or ConicalShellGeometry's row of geom_table / dens_table
+bool packGeometryTable(const Geometry& g, double* t) {
+    if (g.kind != GeometryKind::Torus && g.kind != GeometryKind::ConicalShell) return false;
+    t[0] = g.sinDelta; t[1] = g.sinDeltaIn; t[2] = g.smin; t[3] = g.sdiff;
+    return true;
+}
+constexpr int kDensTab = 101;  // SersicFunction's table length: the rows of dens_table hold 2 * kDensTab doubles
 
 static_assert((int)kDensComponents == (int)SKIRT_DENS_COMPONENTS && (int)kDensNode == (int)SKIRT_DENS_NODE,
               "density sampling modes");
@@ -133,6 +159,8 @@ struct DeviceDensitySampler final : DensitySampler {
         int ntab = 0;
         for (int h = 0; h < nc; h++)
             if (dust[h].geom.kind == GeometryKind::Sersic) ntab = std::max(ntab, (int)dust[h].geom.sv.size());
+            else if (dust[h].geom.kind == GeometryKind::Torus || dust[h].geom.kind == GeometryKind::ConicalShell)
+                ntab = std::max(ntab, kDensTab);
         if (ntab) table.assign(2 * (size_t)ntab * nc, 0.0);
         for (int h = 0; h < nc; h++) {
             const Geometry& g = dust[h].geom;
@@ -144,6 +172,7 @@ struct DeviceDensitySampler final : DensitySampler {
                 std::copy(g.sv.begin(), g.sv.end(), table.begin() + 2 * (size_t)ntab * h);
                 std::copy(g.Sv.begin(), g.Sv.end(), table.begin() + 2 * (size_t)ntab * h + ntab);
             }
+            packGeometryTable(g, &table[ntab ? 2 * (size_t)ntab * h : 0]);
         }
         const SkirtDensityDesc d{nc, kind.data(), param.data(), norm.data(), ntab ? table.data() : nullptr, ntab};
         const int rc = skirt_mcrt_sample_density(device, &d, boxes, n, words, nsample, mode, out);
@@ -301,6 +330,10 @@ void buildDescs(const Model& m, Descs& d) {
                 d.gt[202 * (size_t)h + 101 + q] = g.Mv[q];
             }
         }
+        if (g.kind == GeometryKind::Torus || g.kind == GeometryKind::ConicalShell) {
+            d.gt.resize(202 * (size_t)ns, 0.0);
+            packGeometryTable(g, &d.gt[202 * (size_t)h]);
+        }
         for (int ell = 0; ell < Nl; ell++) d.lum[h * Nl + ell] = m.starL[h][ell];
     }
     for (int ell = 0; ell < Nl; ell++)
@@ -359,6 +392,31 @@ int skirt_sim_describe(SkirtSim* s, const char* path) {
 }
 
 SkirtMcrt* skirt_sim_engine(SkirtSim* s) { return s ? s->eng : nullptr; }
+
+int skirt_sim_sample_positions(SkirtSim* s, int comp, int device, uint64_t seed, uint64_t first, size_t n, double* pos,
+                               int32_t* draws) {
+    if (!s || (n && !pos)) return SKIRT_ERR_ARG;
+    if (comp < 0 || comp >= (int)s->m.starGeom.size()) {
+        g_err = "no stellar component " + std::to_string(comp);
+        return SKIRT_ERR_ARG;
+    }
+    if (device >= 0) {
+        if (!s->eng) { g_err = "no engine attached"; return SKIRT_ERR_STATE; }
+        return check(s, skirt_mcrt_sample_positions(s->eng, comp, seed, first, n, pos, draws));
+    }
+    // the host's position templates (model.hpp) on the engine's per-packet streams
+    const Geometry& g = s->m.starGeom[comp];
+    for (size_t i = 0; i < n; i++) {
+        skirt_dev::PacketRng rng;
+        rng.start(seed, SKIRT_POSITIONS_TAG, first + i);
+        if (!geometryPosition(g, rng, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2])) {
+            g_err = "a TorusGeometry or ConicalShellGeometry found no position in 65536 attempts";
+            return SKIRT_ERR_NUMERIC;
+        }
+        if (draws) draws[i] = (int32_t)(2u * rng.block - (rng.have ? 1u : 0u));
+    }
+    return SKIRT_OK;
+}
 
 int skirt_sim_run_stellar(SkirtSim* s, uint64_t first, uint64_t count) {
     if (!s || !s->eng) { g_err = "no engine attached"; return SKIRT_ERR_STATE; }
