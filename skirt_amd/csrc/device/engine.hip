@@ -30,6 +30,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "vor_terms.hpp"
@@ -54,11 +55,7 @@ constexpr int kLabsBuf = SKIRT_LABS_BUF;  // buffered Labs adds per trace lane (
 #define SKIRT_VOR_DRAIN2 1
 #endif
 constexpr int kStepsPerPull = 4;  // grid steps between two ray pulls of a trace wave
-// The slot pool runs as one or two independent pipelines ("halves", SkirtMcrt::halves): with two, one
-// half's event and detect kernels run beside the other half's trace kernel, on CUs of their own (CU-masked
-// streams, see runPhase).
-constexpr int kMaxHalves = 2;
-// device counters per pipeline half (Args::ctr): 16, each on a 128-byte line of its own (kCtrStride words
+// device counters of the pipeline (Args::ctr): 16, each on a 128-byte line of its own (kCtrStride words
 // apart). The event kernel's block reservations add to four of them every round; packed in one line, those
 // atomics serialized on it: C3 +2.1 %, C2 +6.9 %, C4 +0.5 % apart (profiles/r05_ctr_lines_ab.txt)
 constexpr int kCtrStride = 32;
@@ -69,8 +66,8 @@ constexpr const char* kGeomCapMessage =
     "a TorusGeometry or ConicalShellGeometry found no position in 65536 attempts";
 constexpr int kSersicTable = 202;  // SersicFunction: 101 radii, then 101 cumulative masses
 constexpr int kDetectCopies = 8;   // most LDS copies of the SED sums in the detect kernel (one per 8 lanes)
-constexpr int kPollEvery = 1;      // iterations between two counter copies of a half
-constexpr int kPollRing = 3;       // copies in flight per half (the host reads each kPollRing copies late)
+constexpr int kPollEvery = 1;      // iterations between two counter copies
+constexpr int kPollRing = 3;       // copies in flight (the host reads each kPollRing copies late)
 // occupancy of the trace kernel: 3 waves per SIMD, i.e. at most 168 VGPRs (the grid entry on the pull
 // path would otherwise take the octree kernel to 175 and 2 waves; C3 1.91e8 -> 2.15e8 pkt/s at 3). The
 // Voronoi walk has its own kernel and attribute below.
@@ -3307,26 +3304,18 @@ struct SkirtMcrt {
     unsigned long long *dClaim = nullptr, *dStats = nullptr;
     unsigned long long* dCrossed = nullptr;  // kCrossedCopies x crossedBins (skirt_mcrt_set_crossed)
     int crossedBins = 0;
-    unsigned int *dError = nullptr, *dCtr = nullptr, *hCtr = nullptr;  // kMaxHalves x 8 counters; hCtr: poll ring
-    // the pipeline's streams: sE runs the event, continuous peel-off and detect kernels, sT[h] the trace
-    // kernels of half h; with CU masks (cusT, cusE) they run on disjoint sets of CUs. One half without
-    // masks runs everything on the caller's stream.
-    int halves = 1, cusT = 0, cusE = 0;  // requested (SKIRT_AMD_HALVES, SKIRT_AMD_TRACE_CUS, SKIRT_AMD_EVENT_CUS)
-    hipStream_t sE = nullptr, sT[kMaxHalves] = {};
-    int streamCusT = -1, streamCusE = -1;  // the masks the owned streams were created with
-    int nCusT = 0, nCusE = 0;              // CUs behind each stream (grid sizes)
-    hipEvent_t evFork = nullptr, evJoin[1 + kMaxHalves] = {}, evE[kMaxHalves] = {}, evT[kMaxHalves] = {};
-    // one half without masks: the detect kernel of iteration k runs on sD, beside the event and trace kernels
-    // of iteration k + 1 on the caller's stream (the detection records alternate between two regions by
+    unsigned int *dError = nullptr, *dCtr = nullptr, *hCtr = nullptr;  // kCtrWords counters; hCtr: poll ring
+    // The pipeline runs on the caller's stream. The detect kernel of iteration k may run on sD, beside the
+    // event and trace kernels of iteration k + 1 (the detection records alternate between two regions by
     // iteration parity, Args::det); evDet[q]: the detect kernel of the last parity-q iteration is done
     hipStream_t sD = nullptr;
     hipEvent_t evDetT = nullptr, evDet[2] = {}, evDetJoin = nullptr;
-    std::vector<hipEvent_t> pollEv;      // kMaxHalves x kPollRing events behind the counter copies
+    std::vector<hipEvent_t> pollEv;      // kPollRing events behind the counter copies
     // slot pool
-    int nslots = 0, rayCap = 0, poolHalves = 0;
+    int nslots = 0, rayCap = 0;
     bool poolPath = false;  // the pool holds the continuous-scattering path records
     bool poolDetPair = false;  // the pool holds two detection-record regions (one per iteration parity)
-    void* dPool = nullptr;               // one pool of nslots slots per half
+    void* dPool = nullptr;               // nslots slots
     size_t poolBytes = 0;
     // config
     // threshold 0: 16 idle lanes before a trace wave pulls rays, 8 on Voronoi grids (C3 +0.6 %, C2 +0.5 %, C5
@@ -3378,75 +3367,105 @@ int upload(SkirtMcrt* c, T*& dst, const T* src, size_t n) {
     return SKIRT_OK;
 }
 
-// slot pool: one pool per pipeline half, each with its ray queue, SoA packet state, per-slot
-// results and two active lists; nslots counts the slots of one half
+// The grid walks the host side knows, each listed once: the Grid<> kind its kernels are instantiated for, its
+// SkirtStats::grid_walk value, and whether the walk's mesh is staged in LDS (nx + ny + nz + 3 doubles). The
+// node-array tree walk comes last: withWalk falls back to it.
+struct Walk {
+    int kind, stat;
+    bool meshInLds;
+};
+constexpr Walk kWalks[] = {
+    {SKIRT_GRID_CARTESIAN, SKIRT_WALK_CARTESIAN, true},
+    {SKIRT_GRID_OCTREE, SKIRT_WALK_OCTREE_MAP, false},  // octree leaf map
+    {kBinTreeMap, SKIRT_WALK_KDTREE_MAP, false},
+    {kOctreeBookkeeping, SKIRT_WALK_OCTREE_BOOKKEEPING, false},
+    {SKIRT_GRID_CYLINDER2D, SKIRT_WALK_CYLINDER2D, true},
+    {SKIRT_GRID_SPHERE1D, SKIRT_WALK_SPHERE1D, true},
+    {SKIRT_GRID_SPHERE2D, SKIRT_WALK_SPHERE2D, true},
+    {SKIRT_GRID_VORONOI, SKIRT_WALK_VORONOI, false},
+    {kOctreeNodes, SKIRT_WALK_TREE_NODES, false},
+};
+constexpr int kNumWalks = (int)(sizeof kWalks / sizeof kWalks[0]);
+
+const Walk& walkOf(int kind) {
+    for (const Walk& w : kWalks)
+        if (w.kind == kind) return w;
+    return kWalks[kNumWalks - 1];
+}
+
+// f(std::integral_constant<int, G>{}) for the walk kind G = kind: the one place where a runtime grid kind
+// turns into a template argument. A generic lambda is instantiated for every kind, so it names only the
+// kernels that exist for each (if constexpr). The kinds are instantiated in the table's order, which is
+// the order the kernels have always had in the code object.
+template <int I = 0, class F>
+auto withWalk(int kind, F&& f) {
+    if constexpr (I + 1 < kNumWalks) {
+        if (kind == kWalks[I].kind) return f(std::integral_constant<int, kWalks[I].kind>{});
+        return withWalk<I + 1>(kind, f);
+    } else {
+        return f(std::integral_constant<int, kWalks[I].kind>{});
+    }
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a runtime flag as a template argument
+template <class F>
+auto withBool(bool b, F&& f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// the walk of the uploaded grid; trees go through their leaf map where there is one and the phase has dust
+int walkKind(const SkirtMcrt* c, bool hasDust) {
+    if (c->gridKind < 0) return kOctreeNodes;  // no grid (a dust-free simulation): nothing is walked
+    if (c->gridKind != SKIRT_GRID_OCTREE) return c->gridKind;
+    if (c->search == SKIRT_TREE_BOOKKEEPING) return kOctreeBookkeeping;
+    if (c->mapL >= 0 && hasDust) return c->binTree ? kBinTreeMap : SKIRT_GRID_OCTREE;
+    return kOctreeNodes;
+}
+
+// the trace kernel of a walk; a phase storing no absorption may run traceKernelNoStore (no Voronoi one exists)
+const void* traceKernelOf(int kind, bool one, bool continuous, bool global, bool noStore) {
+    return withWalk(kind, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        if constexpr (G != SKIRT_GRID_VORONOI)
+            if (noStore) return (const void*)traceKernelNoStore<G>;
+        return withBool(global, [&](auto gl) {
+            constexpr bool L = decltype(gl)::value;
+            if constexpr (G == SKIRT_GRID_VORONOI) {
+                if (!continuous) return one ? (const void*)traceKernelVor<true, false, L> : (const void*)traceKernelVor<false, false, L>;
+                return one ? (const void*)traceKernelVor<true, true, L> : (const void*)traceKernelVor<false, true, L>;
+            } else {
+                if (!continuous) return one ? (const void*)traceKernel<G, true, false, L> : (const void*)traceKernel<G, false, false, L>;
+                return one ? (const void*)traceKernel<G, true, true, L> : (const void*)traceKernel<G, false, true, L>;
+            }
+        });
+    });
+}
+
+// slot pool: the ray queue, SoA packet state, per-slot results and two active lists of nslots slots
 // With continuous scattering every slot may also queue one peel-off per instrument and recorded path
 // segment in one iteration, and keeps the dust segments of its last path (kPathCap each).
-int ensurePool(SkirtMcrt* c, int nslots, bool continuous, int halves, bool detPair) {
+int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair) {
     const int ninstr = (int)c->instr.size();
     const size_t rays = (size_t)nslots * (1 + ninstr) + (continuous ? (size_t)nslots * kPathCap * ninstr : 0);
     if (rays >= (size_t)INT32_MAX) return fail(c, SKIRT_ERR_UNSUPPORTED, "ray queue too large");
     const int rayCap = (int)rays;
     const size_t path = continuous ? (size_t)nslots * (kPathCap * sizeof(PathRec) + sizeof(int)) : 0;
-    const size_t half = (size_t)rayCap * sizeof(RayRec) + (detPair ? 2 : 1) * (size_t)(rayCap - nslots) * sizeof(DetRec) +
-                        (size_t)nslots * (10 * 8 + 5 * 4 + 6 * 4 + 2 * 4) + path + 4096;
-    if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolPath == (path > 0) && c->poolHalves == halves &&
-        c->poolDetPair == detPair)
+    const size_t bytes = (size_t)rayCap * sizeof(RayRec) + (detPair ? 2 : 1) * (size_t)(rayCap - nslots) * sizeof(DetRec) +
+                         (size_t)nslots * (10 * 8 + 5 * 4 + 6 * 4 + 2 * 4) + path + 4096;
+    if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolPath == (path > 0) && c->poolDetPair == detPair)
         return SKIRT_OK;
     c->poolPath = path > 0;
     c->poolDetPair = detPair;
     if (c->dPool) { (void)hipFree(c->dPool); c->dPool = nullptr; }
-    HIPCHECK(c, hipMalloc(&c->dPool, halves * half));
-    c->poolBytes = half;
+    HIPCHECK(c, hipMalloc(&c->dPool, bytes));
+    c->poolBytes = bytes;
     c->nslots = nslots;
     c->rayCap = rayCap;
-    c->poolHalves = halves;
     return SKIRT_OK;
 }
 
-// A stream restricted to `want` CUs (0: all), spread evenly over the XCDs: CU k of the mask is taken when
-// k mod 32 < want / 8 (or, for the complementary set, k mod 32 >= 32 - want / 8), so that each XCD
-// contributes the same share whether the runtime numbers CUs XCD by XCD or round-robin.
-int makeStream(SkirtMcrt* c, hipStream_t* s, int want, bool high, int* got) {
-    if (want <= 0 || want >= c->numCUs) {
-        *got = c->numCUs;
-        HIPCHECK(c, hipStreamCreateWithFlags(s, hipStreamNonBlocking));
-        return SKIRT_OK;
-    }
-    const int words = (c->numCUs + 31) / 32;
-    std::vector<uint32_t> mask(words, 0u);
-    const int per = std::max(1, want * 32 / std::max(32, c->numCUs));
-    int n = 0;
-    for (int k = 0; k < c->numCUs; k++) {
-        const int r = k % 32;
-        if (high ? r >= 32 - per : r < per) { mask[k / 32] |= 1u << (k % 32); n++; }
-    }
-    *got = n;
-    HIPCHECK(c, hipExtStreamCreateWithCUMask(s, (uint32_t)words, mask.data()));
-    return SKIRT_OK;
-}
-
-// the pipeline streams for the requested halves and CU masks (created once per mask configuration)
-int ensureStreams(SkirtMcrt* c) {
-    if (c->halves == 1 && c->cusT == 0 && c->cusE == 0) {
-        c->nCusT = c->nCusE = c->numCUs;
-        return SKIRT_OK;  // everything on the caller's stream
-    }
-    if (c->sE && c->streamCusT == c->cusT && c->streamCusE == c->cusE) return SKIRT_OK;
-    (void)hipStreamSynchronize(c->stream);
-    if (c->sE) { (void)hipStreamDestroy(c->sE); c->sE = nullptr; }
-    for (auto& s : c->sT)
-        if (s) { (void)hipStreamDestroy(s); s = nullptr; }
-    int rc = makeStream(c, &c->sE, c->cusE, true, &c->nCusE);
-    for (int h = 0; h < kMaxHalves && !rc; h++) rc = makeStream(c, &c->sT[h], c->cusT, false, &c->nCusT);
-    if (rc) return rc;
-    c->streamCusT = c->cusT;
-    c->streamCusE = c->cusE;
-    return SKIRT_OK;
-}
-
-void carvePool(SkirtMcrt* c, Args& a, int h) {
-    char* p = static_cast<char*>(c->dPool) + (size_t)h * c->poolBytes;
+void carvePool(SkirtMcrt* c, Args& a) {
+    char* p = static_cast<char*>(c->dPool);
     const size_t n = (size_t)c->nslots;
     auto takeD = [&](double*& d) { d = reinterpret_cast<double*>(p); p += n * 8; };
     auto takeI = [&](int*& d) { d = reinterpret_cast<int*>(p); p += n * 4; };
@@ -3470,7 +3489,7 @@ void carvePool(SkirtMcrt* c, Args& a, int h) {
     }
     a.nslots = c->nslots;
     a.rayCap = c->rayCap;
-    a.ctr = c->dCtr + kCtrWords * h;
+    a.ctr = c->dCtr;
 }
 
 // Decides whether the octree can be walked through a leaf map (Grid<SKIRT_GRID_OCTREE>): every node
@@ -3712,27 +3731,11 @@ int skirt_mcrt_create(int device, SkirtMcrt** out) {
         hipMalloc(&c->dClaim, sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc(&c->dStats, 8 * kStatCopies * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc(&c->dError, sizeof(unsigned int)) != hipSuccess ||
-        hipMalloc(&c->dCtr, kMaxHalves * kCtrWords * sizeof(unsigned int)) != hipSuccess ||
-        hipHostMalloc(&c->hCtr, kMaxHalves * kPollRing * kCtrWords * sizeof(unsigned int)) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming) != hipSuccess) {
-        delete c;
+        hipMalloc(&c->dCtr, kCtrWords * sizeof(unsigned int)) != hipSuccess ||
+        hipHostMalloc(&c->hCtr, kPollRing * kCtrWords * sizeof(unsigned int)) != hipSuccess) {
+        skirt_mcrt_destroy(c);  // frees what the failed step left allocated
         return SKIRT_ERR_HIP;
     }
-    for (int h = 0; h < kMaxHalves; h++)
-        if (hipEventCreateWithFlags(&c->evE[h], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->evT[h], hipEventDisableTiming) != hipSuccess) {
-            delete c;
-            return SKIRT_ERR_HIP;
-        }
-    for (auto& e : c->evJoin)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-            delete c;
-            return SKIRT_ERR_HIP;
-        }
-    // pipeline layout (tuning knobs; see runPhase)
-    if (const char* s = getenv("SKIRT_AMD_HALVES")) c->halves = std::max(1, std::min(kMaxHalves, atoi(s)));
-    if (const char* s = getenv("SKIRT_AMD_TRACE_CUS")) c->cusT = std::max(0, atoi(s));
-    if (const char* s = getenv("SKIRT_AMD_EVENT_CUS")) c->cusE = std::max(0, atoi(s));
     c->stream = c->own;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
@@ -3760,327 +3763,358 @@ int skirt_mcrt_configure(SkirtMcrt* c, int slots, int grid, int threshold) {
     return SKIRT_OK;
 }
 
+// n cells between n + 1 strictly increasing points (none: nothing to check)
+static bool increasing(const double* v, int n) {
+    for (int i = 0; i < n; i++)
+        if (!(v[i] < v[i + 1])) return false;
+    return true;
+}
+
+// SKIRT_AMD_CELL_ALIGN=0: the reference's cell order, without the line-aligned device numbering
+static bool cellAlign() {
+    const char* env = getenv("SKIRT_AMD_CELL_ALIGN");
+    return !(env && env[0] == '0');
+}
+
+// The mesh of the Cartesian, cylindrical and spherical grids: the points of each axis in turn, nx + 1 | ny + 1 |
+// nz + 1 doubles; an axis without cells (n = 0) keeps one unused word.
+static int uploadMesh(SkirtMcrt* c, const double* xv, int nx, const double* yv, int ny, const double* zv, int nz) {
+    std::vector<double> mesh;
+    auto axis = [&](const double* v, int n) {
+        if (n > 0) mesh.insert(mesh.end(), v, v + n + 1);
+        else mesh.push_back(0.0);
+    };
+    axis(xv, nx);
+    axis(yv, ny);
+    axis(zv, nz);
+    c->nx = nx; c->ny = ny; c->nz = nz;
+    return upload(c, c->dMesh, mesh.data(), mesh.size());
+}
+
+static int uploadCartesian(SkirtMcrt* c, const SkirtGridDesc* g) {
+    if (g->nx < 1 || g->ny < 1 || g->nz < 1 || !g->xv || !g->yv || !g->zv) return fail(c, SKIRT_ERR_ARG, "bad Cartesian grid");
+    if ((long long)g->nx * g->ny * g->nz != g->ncells) return fail(c, SKIRT_ERR_ARG, "ncells != nx*ny*nz");
+    if (!increasing(g->xv, g->nx)) return fail(c, SKIRT_ERR_ARG, "x mesh not increasing");
+    if (!increasing(g->yv, g->ny)) return fail(c, SKIRT_ERR_ARG, "y mesh not increasing");
+    if (!increasing(g->zv, g->nz)) return fail(c, SKIRT_ERR_ARG, "z mesh not increasing");
+    // device numbers in 2x2x2 bricks (Grid<SKIRT_GRID_CARTESIAN>::dev); SKIRT_AMD_CELL_ALIGN=0: the
+    // reference's numbering
+    c->brick = cellAlign();
+    if (c->brick) {
+        const long long bx = (g->nx + 1) / 2, by = (g->ny + 1) / 2, bz = (g->nz + 1) / 2;
+        if (8 * bx * by * bz >= (1ll << 31)) return fail(c, SKIRT_ERR_UNSUPPORTED, "Cartesian grid too large");
+        c->devCell.assign(g->ncells, 0);
+        for (int i = 0; i < g->nx; i++)
+            for (int j = 0; j < g->ny; j++)
+                for (int k = 0; k < g->nz; k++)
+                    c->devCell[k + g->nz * j + g->nz * g->ny * i] =
+                        (int)((((i >> 1) * by + (j >> 1)) * bz + (k >> 1)) << 3) | ((i & 1) << 2) | ((j & 1) << 1) | (k & 1);
+        c->ndev = (int)(8 * bx * by * bz);
+    }
+    c->gx0 = g->xv[0]; c->gx1 = g->xv[g->nx];
+    c->gy0 = g->yv[0]; c->gy1 = g->yv[g->ny];
+    c->gz0 = g->zv[0]; c->gz1 = g->zv[g->nz];
+    return uploadMesh(c, g->xv, g->nx, g->yv, g->ny, g->zv, g->nz);
+}
+
+// Morton order of the leaves: depth-first, children in octant order (x, y, z bits). A ray crosses
+// about 2.5 of the 8 children of a node it enters, so 8 sibling leaves are numbered from a
+// multiple of 8 (one 64-byte line of every Labs row), leaving unused device cells before them:
+// the ray's Labs adds into them then share one atomic request (SKIRT_AMD_CELL_ALIGN=0: no gaps).
+static int numberTreeLeaves(SkirtMcrt* c, const SkirtGridDesc* g) {
+    c->devCell.assign(g->ncells, -1);
+    const int arity = g->split_dir ? 2 : 8;
+    const bool align = arity == 8 && cellAlign();
+    std::vector<int> stack{0};
+    int next = 0, used = 0;
+    auto number = [&](int l) -> bool {
+        if (c->devCell[g->cellnumber[l]] >= 0) return false;
+        c->devCell[g->cellnumber[l]] = next++;
+        used++;
+        return true;
+    };
+    while (!stack.empty()) {
+        const int l = stack.back();
+        stack.pop_back();
+        const int fc = g->first_child[l];
+        if (fc < 0) {
+            if (!number(l)) return fail(c, SKIRT_ERR_ARG, "octree cell number used twice");
+            continue;
+        }
+        bool leaves = align;
+        for (int k = 0; k < arity && leaves; k++) leaves = g->first_child[fc + k] < 0;
+        if (leaves) {  // the sibling leaves, aligned: the same depth-first order
+            next = (next + 7) & ~7;
+            for (int k = 0; k < arity; k++)
+                if (!number(fc + k)) return fail(c, SKIRT_ERR_ARG, "octree cell number used twice");
+        } else {
+            for (int k = arity - 1; k >= 0; k--) stack.push_back(fc + k);
+        }
+    }
+    if (used != g->ncells) return fail(c, SKIRT_ERR_ARG, "octree leaves do not cover the cells");
+    c->ndev = next;
+    return SKIRT_OK;
+}
+
+static int uploadTree(SkirtMcrt* c, const SkirtGridDesc* g) {
+    if (g->nnodes < 1 || !g->box || !g->first_child || !g->cellnumber || !g->nbr_offset)
+        return fail(c, SKIRT_ERR_ARG, "bad octree grid");
+    // validate the index arrays so that the kernels never read out of bounds
+    const bool bin = g->split_dir != nullptr;
+    const int arity = bin ? 2 : 8;
+    int nleaf = 0;
+    for (int l = 0; l < g->nnodes; l++) {
+        const int fc = g->first_child[l];
+        if (fc >= 0 && (fc + arity > g->nnodes || fc <= l)) return fail(c, SKIRT_ERR_ARG, "octree child index out of range");
+        if (fc >= 0 && bin && (g->split_dir[l] < 0 || g->split_dir[l] > 2)) return fail(c, SKIRT_ERR_ARG, "bad k-d tree split axis");
+        if (fc < 0) {
+            if (g->cellnumber[l] < 0 || g->cellnumber[l] >= g->ncells) return fail(c, SKIRT_ERR_ARG, "octree cell number out of range");
+            nleaf++;
+        }
+    }
+    if (nleaf != g->ncells) return fail(c, SKIRT_ERR_ARG, "octree leaf count != ncells");
+    const int nnbr = g->nbr_offset[6 * (size_t)g->nnodes];
+    for (size_t q = 0; q < 6 * (size_t)g->nnodes; q++)
+        if (g->nbr_offset[q] < 0 || g->nbr_offset[q] > g->nbr_offset[q + 1]) return fail(c, SKIRT_ERR_ARG, "bad neighbor offsets");
+    for (int q = 0; q < nnbr; q++)
+        if (g->nbr_list[q] < 0 || g->nbr_list[q] >= g->nnodes) return fail(c, SKIRT_ERR_ARG, "neighbor index out of range");
+    if (g->search < SKIRT_TREE_TOPDOWN || g->search > SKIRT_TREE_BOOKKEEPING) return fail(c, SKIRT_ERR_ARG, "bad tree search method");
+    std::vector<int> father;
+    if (g->search == SKIRT_TREE_BOOKKEEPING) {
+        // the Bookkeeping search reads octants off the breadth-first numbering: every group of
+        // children must start at an id = 1 (mod 8) (TreeDustGrid.cpp:525)
+        if (bin) return fail(c, SKIRT_ERR_ARG, "Bookkeeping method is not compatible with binary tree");
+        father.assign(g->nnodes, -1);
+        for (int l = 0; l < g->nnodes; l++) {
+            const int fc = g->first_child[l];
+            if (fc < 0) continue;
+            if ((fc - 1) % 8 != 0) return fail(c, SKIRT_ERR_ARG, "octree not numbered breadth-first for the Bookkeeping search");
+            for (int k = 0; k < 8; k++) father[fc + k] = l;
+        }
+    }
+    c->nnodes = g->nnodes;
+    c->eps = g->eps;
+    c->search = g->search;
+    c->gx0 = g->box[0]; c->gy0 = g->box[1]; c->gz0 = g->box[2];
+    c->gx1 = g->box[3]; c->gy1 = g->box[4]; c->gz1 = g->box[5];
+    int rc;
+    if ((rc = upload(c, c->dBox, g->box, 6 * (size_t)g->nnodes))) return rc;
+    if ((rc = upload(c, c->dFirstChild, g->first_child, (size_t)g->nnodes))) return rc;
+    c->binTree = bin;
+    if (!father.empty() && (rc = upload(c, c->dFather, father.data(), father.size()))) return rc;
+    if (bin) {
+        std::vector<signed char> dirs(g->split_dir, g->split_dir + g->nnodes);
+        for (int l = 0; l < g->nnodes; l++)
+            if (g->first_child[l] < 0) dirs[l] = 0;
+        if ((rc = upload(c, c->dSplitDir, dirs.data(), dirs.size()))) return rc;
+    }
+    if ((rc = numberTreeLeaves(c, g))) return rc;
+    std::vector<int> cellNode(g->ncells, 0);
+    for (int l = 0; l < g->nnodes; l++)
+        if (g->first_child[l] < 0) cellNode[g->cellnumber[l]] = l;
+    if ((rc = upload(c, c->dCellNode, cellNode.data(), cellNode.size()))) return rc;
+    std::vector<int> cn(g->cellnumber, g->cellnumber + g->nnodes);
+    for (int l = 0; l < g->nnodes; l++)
+        if (cn[l] >= 0) cn[l] = c->devCell[cn[l]];
+    if ((rc = upload(c, c->dCellnumber, cn.data(), (size_t)g->nnodes))) return rc;
+    if ((rc = upload(c, c->dNbrOffset, g->nbr_offset, 6 * (size_t)g->nnodes + 1))) return rc;
+    std::vector<int> dummy(1, 0);
+    if ((rc = upload(c, c->dNbrList, nnbr ? g->nbr_list : dummy.data(), nnbr ? (size_t)nnbr : 1))) return rc;
+    return planLeafMap(c, g);
+}
+
+// device cell numbers in Morton order of the sites (21 bits per axis, ties by reference number):
+// cells adjacent in space are adjacent in memory, for the neighbour lists, the densities and the
+// Labs tallies alike. Every list keeps its reference order (first-minimum choices depend on it).
+static void numberVoronoiCells(SkirtMcrt* c, const SkirtGridDesc* g) {
+    const int N = g->ncells;
+    c->devCell.assign(N, 0);
+    std::vector<std::pair<uint64_t, int>> key(N);
+    const double ext[3] = {c->gx1 - c->gx0, c->gy1 - c->gy0, c->gz1 - c->gz0};
+    const double lo[3] = {c->gx0, c->gy0, c->gz0};
+    for (int m = 0; m < N; m++) {
+        uint64_t code = 0;
+        for (int d = 0; d < 3; d++) {
+            const double f = (g->site[3 * (size_t)m + d] - lo[d]) / ext[d];
+            const uint64_t u = (uint64_t)std::max(0.0, std::min(2097151.0, f * 2097152.0));
+            for (int bit = 0; bit < 21; bit++) code |= ((u >> bit) & 1ull) << (3 * bit + (2 - d));
+        }
+        key[m] = {code, m};
+    }
+    std::sort(key.begin(), key.end());
+    for (int q = 0; q < N; q++) c->devCell[key[q].second] = q;
+}
+
+static int uploadVoronoi(SkirtMcrt* c, const SkirtGridDesc* g) {
+    const int N = g->ncells;
+    if (N < 1 || !g->site || !g->cell_nbr_offset || !g->cell_nbr_list || !g->cell_bbox || g->nblocks < 1 ||
+        !g->block_offset || !g->block_list)
+        return fail(c, SKIRT_ERR_ARG, "bad Voronoi grid");
+    if (N > kCellMaskOut) return fail(c, SKIRT_ERR_UNSUPPORTED, "more than 2^28 Voronoi cells");
+    const int nnbr = g->cell_nbr_offset[N];
+    for (int m = 0; m < N; m++)
+        if (g->cell_nbr_offset[m] < 0 || g->cell_nbr_offset[m] > g->cell_nbr_offset[m + 1])
+            return fail(c, SKIRT_ERR_ARG, "bad Voronoi neighbour offsets");
+    for (int q = 0; q < nnbr; q++)
+        if (g->cell_nbr_list[q] < -6 || g->cell_nbr_list[q] >= N) return fail(c, SKIRT_ERR_ARG, "Voronoi neighbour out of range");
+    const size_t nb3 = (size_t)g->nblocks * g->nblocks * g->nblocks;
+    const int nbl = g->block_offset[nb3];
+    for (int q = 0; q < nbl; q++)
+        if (g->block_list[q] < 0 || g->block_list[q] >= N) return fail(c, SKIRT_ERR_ARG, "Voronoi block list out of range");
+    c->eps = g->eps;
+    c->gx0 = g->extent[0]; c->gy0 = g->extent[1]; c->gz0 = g->extent[2];
+    c->gx1 = g->extent[3]; c->gy1 = g->extent[4]; c->gz1 = g->extent[5];
+    c->vnb = g->nblocks;
+    numberVoronoiCells(c, g);
+    std::vector<int> refOf(N);
+    for (int m = 0; m < N; m++) refOf[c->devCell[m]] = m;
+    std::vector<double> site(3 * (size_t)N), bbox(6 * (size_t)N);
+    // each device cell's block: kVorHead header slots + one slot per neighbour, in pairs (see VorEntry);
+    // the array is padded by kVorPad slots, since a step loads whole groups of entries
+    std::vector<int> start(N + 1, 0);
+    for (int d = 0; d < N; d++) {
+        const int m = refOf[d];
+        const int cnt = g->cell_nbr_offset[m + 1] - g->cell_nbr_offset[m];
+        if (cnt < 1) return fail(c, SKIRT_ERR_ARG, "Voronoi cell without neighbours");
+        // whole groups of kVorUnroll entries (even)
+        const int per = kVorUnroll;
+        start[d + 1] = start[d] + kVorHead + (cnt + per - 1) / per * per;
+    }
+    if ((size_t)start[N] + kVorPad >= (size_t)INT32_MAX) return fail(c, SKIRT_ERR_UNSUPPORTED, "Voronoi mesh too large");
+    std::vector<VorEntry> slots((size_t)start[N] + kVorPad, VorEntry{0.f, 0.f, 0.f, -1});
+    // offsets in units of the domain's largest half-width: single-precision squares stay in range
+    c->vorScale = 2.0 / std::max({c->gx1 - c->gx0, c->gy1 - c->gy0, c->gz1 - c->gz0});
+    for (int d = 0; d < N; d++) {
+        const int m = refOf[d];
+        const double* sm = g->site + 3 * (size_t)m;
+        for (int q = 0; q < 3; q++) site[3 * (size_t)d + q] = sm[q];
+        for (int q = 0; q < 6; q++) bbox[6 * (size_t)d + q] = g->cell_bbox[6 * (size_t)m + q];
+        VorEntry* blk = slots.data() + start[d];
+        const double head[4] = {sm[0], sm[1], sm[2], 0.0};  // rho of component 0: set by upload_media
+        std::memcpy(blk, head, sizeof head);
+        const int cnt = g->cell_nbr_offset[m + 1] - g->cell_nbr_offset[m];
+        std::vector<float> off(3 * (size_t)cnt);
+        int o = 0;
+        for (int q = g->cell_nbr_offset[m]; q < g->cell_nbr_offset[m + 1]; q++, o++) {
+            const int id = g->cell_nbr_list[q];
+            VorEntry e;
+            if (id < 0) {
+                // a wall (-1 xmin, -2 xmax, ... -6 zmax) is the bisector plane of the site and its mirror
+                // image: the offset to the mirror site along the wall's axis (NaN when the site lies on
+                // the wall: the step then evaluates the list exactly)
+                const int axis = (-id - 1) / 2;
+                const double lim[6] = {c->gx0, c->gx1, c->gy0, c->gy1, c->gz0, c->gz1};
+                const double w = lim[-id - 1] - sm[axis];
+                double n[3] = {0.0, 0.0, 0.0};
+                n[axis] = w != 0.0 ? 2.0 * w * c->vorScale : NAN;
+                float o[3];
+                vorRecipOffset(n[0], n[1], n[2], o);  // m = n / |n|^2 (vor_terms.hpp)
+                e = VorEntry{o[0], o[1], o[2], id};
+            } else {
+                const double* si = g->site + 3 * (size_t)id;
+                float o[3];
+                vorRecipOffset((si[0] - sm[0]) * c->vorScale, (si[1] - sm[1]) * c->vorScale,
+                               (si[2] - sm[2]) * c->vorScale, o);
+                e = VorEntry{o[0], o[1], o[2], start[c->devCell[id]]};
+            }
+            // entry o in its pair (see VorEntry): {ox0, ox1, oy0, oy1} {oz0, oz1, next0, next1}
+            float* P = reinterpret_cast<float*>(blk + kVorHead + (o & ~1));
+            const int h = o & 1;
+            P[h] = e.ox; P[2 + h] = e.oy; P[4 + h] = e.oz;
+            std::memcpy(P + 6 + h, &e.next, 4);
+            off[3 * (size_t)o] = e.ox; off[3 * (size_t)o + 1] = e.oy; off[3 * (size_t)o + 2] = e.oz;
+        }
+        // the padding up to the next block: NaN entries, no exit for any direction (bounds())
+        for (int q = cnt; q < start[d + 1] - start[d] - kVorHead; q++) {
+            float* P = reinterpret_cast<float*>(blk + kVorHead + (q & ~1));
+            const int h = q & 1;
+            P[h] = P[2 + h] = P[4 + h] = NAN;
+            const int none = -1;
+            std::memcpy(P + 6 + h, &none, 4);
+        }
+        // the header's last words: id, count and the cell's error terms of the bounds (vor_terms.hpp)
+        float eA, eB;
+        vorRecipErrorTerms(off.data(), cnt, 3, &eA, &eB);
+        int ids[4] = {d, cnt, 0, 0};
+        std::memcpy(&ids[2], &eA, 4);
+        std::memcpy(&ids[3], &eB, 4);
+        std::memcpy(blk + 2, ids, sizeof ids);
+    }
+    c->vorSlotsHost = std::move(slots);
+    std::vector<BlockSite> blocks(std::max(nbl, 1), BlockSite{0.0, 0.0, 0.0, -1, 0});
+    for (int q = 0; q < nbl; q++) {
+        const int m = g->block_list[q];
+        blocks[q] = BlockSite{g->site[3 * (size_t)m], g->site[3 * (size_t)m + 1], g->site[3 * (size_t)m + 2], c->devCell[m], 0};
+    }
+    int rc;
+    if ((rc = upload(c, c->dSite, site.data(), site.size()))) return rc;
+    if ((rc = upload(c, c->dCellBbox, bbox.data(), bbox.size()))) return rc;
+    if ((rc = upload(c, c->dVorStart, start.data(), start.size()))) return rc;
+    if ((rc = upload(c, c->dVorSlots, c->vorSlotsHost.data(), c->vorSlotsHost.size()))) return rc;
+    c->vorStartHost = std::move(start);
+    if ((rc = upload(c, c->dBlockOffset, g->block_offset, nb3 + 1))) return rc;
+    if ((rc = upload(c, c->dBlockSites, blocks.data(), blocks.size()))) return rc;
+    return upload(c, c->dDevCell, c->devCell.data(), c->devCell.size());
+}
+
+static int uploadCylinder(SkirtMcrt* c, const SkirtGridDesc* g) {
+    if (g->nx < 1 || g->nz < 1 || !g->xv || !g->zv) return fail(c, SKIRT_ERR_ARG, "bad cylindrical grid");
+    if ((long long)g->nx * g->nz != g->ncells) return fail(c, SKIRT_ERR_ARG, "ncells != nx*nz");
+    if (g->xv[0] != 0.0) return fail(c, SKIRT_ERR_ARG, "the radial mesh does not start at 0");
+    if (!increasing(g->xv, g->nx)) return fail(c, SKIRT_ERR_ARG, "R mesh not increasing");
+    if (!increasing(g->zv, g->nz)) return fail(c, SKIRT_ERR_ARG, "z mesh not increasing");
+    c->gx0 = -g->xv[g->nx]; c->gx1 = g->xv[g->nx];
+    c->gy0 = -g->xv[g->nx]; c->gy1 = g->xv[g->nx];
+    c->gz0 = g->zv[0]; c->gz1 = g->zv[g->nz];
+    // R | one unused word | z: the Cartesian mesh layout with ny = 0
+    return uploadMesh(c, g->xv, g->nx, nullptr, 0, g->zv, g->nz);
+}
+
+static int uploadSphere(SkirtMcrt* c, const SkirtGridDesc* g) {
+    const bool two = g->kind == SKIRT_GRID_SPHERE2D;
+    const int nt = two ? g->nz : 0;
+    if (g->nx < 1 || !g->xv) return fail(c, SKIRT_ERR_ARG, "bad spherical grid");
+    if (two ? (nt < 1 || g->ny != nt || !g->yv || !g->zv) : (g->ny != 0 || g->nz != 0))
+        return fail(c, SKIRT_ERR_ARG, "bad spherical grid");
+    if ((long long)g->nx * (two ? nt : 1) != g->ncells) return fail(c, SKIRT_ERR_ARG, "ncells != nx*nz");
+    const double rmax = g->extent[3];
+    if (!(rmax > 0.0) || !(g->xv[g->nx - 1] < rmax)) return fail(c, SKIRT_ERR_ARG, "extent does not hold the outer radius");
+    if (g->xv[0] != 0.0) return fail(c, SKIRT_ERR_ARG, "the radial mesh does not start at 0");
+    if (!increasing(g->xv, g->nx)) return fail(c, SKIRT_ERR_ARG, "r mesh not increasing");
+    if (!increasing(g->zv, nt)) return fail(c, SKIRT_ERR_ARG, "theta mesh not increasing");
+    for (int i = 0; i < nt; i++) if (!(g->yv[i] > g->yv[i + 1])) return fail(c, SKIRT_ERR_ARG, "cosines not decreasing");
+    if (two && !(g->eps > 0.0)) return fail(c, SKIRT_ERR_ARG, "eps should be positive");
+    c->gx0 = -rmax; c->gx1 = rmax;
+    c->gy0 = -rmax; c->gy1 = rmax;
+    c->gz0 = -rmax; c->gz1 = rmax;
+    c->eps = two ? g->eps : 0.0;
+    // r | cos theta | theta: the Cartesian mesh layout (one unused word each where ny = nz = 0)
+    return uploadMesh(c, g->xv, g->nx, g->yv, nt, g->zv, nt);
+}
+
 int skirt_mcrt_upload_grid(SkirtMcrt* c, const SkirtGridDesc* g) {
     if (!c || !g) return SKIRT_ERR_ARG;
     HIPCHECK(c, hipSetDevice(c->device));
+    c->gridKind = -1;  // a rejected upload leaves no grid
     c->ncells = g->ncells;
     c->ndev = g->ncells;
+    // the state only some grids set
     c->brick = false;
     c->devCell.clear();
-    if (g->kind == SKIRT_GRID_CARTESIAN) {
-        if (g->nx < 1 || g->ny < 1 || g->nz < 1 || !g->xv || !g->yv || !g->zv) return fail(c, SKIRT_ERR_ARG, "bad Cartesian grid");
-        if ((long long)g->nx * g->ny * g->nz != g->ncells) return fail(c, SKIRT_ERR_ARG, "ncells != nx*ny*nz");
-        std::vector<double> mesh;
-        mesh.insert(mesh.end(), g->xv, g->xv + g->nx + 1);
-        mesh.insert(mesh.end(), g->yv, g->yv + g->ny + 1);
-        mesh.insert(mesh.end(), g->zv, g->zv + g->nz + 1);
-        for (int i = 0; i < g->nx; i++) if (!(g->xv[i] < g->xv[i + 1])) return fail(c, SKIRT_ERR_ARG, "x mesh not increasing");
-        for (int i = 0; i < g->ny; i++) if (!(g->yv[i] < g->yv[i + 1])) return fail(c, SKIRT_ERR_ARG, "y mesh not increasing");
-        for (int i = 0; i < g->nz; i++) if (!(g->zv[i] < g->zv[i + 1])) return fail(c, SKIRT_ERR_ARG, "z mesh not increasing");
-        c->nx = g->nx; c->ny = g->ny; c->nz = g->nz;
-        // device numbers in 2x2x2 bricks (Grid<SKIRT_GRID_CARTESIAN>::dev); SKIRT_AMD_CELL_ALIGN=0: the
-        // reference's numbering
-        const char* alignEnv = getenv("SKIRT_AMD_CELL_ALIGN");
-        c->brick = !(alignEnv && alignEnv[0] == '0');
-        if (c->brick) {
-            const long long bx = (g->nx + 1) / 2, by = (g->ny + 1) / 2, bz = (g->nz + 1) / 2;
-            if (8 * bx * by * bz >= (1ll << 31)) return fail(c, SKIRT_ERR_UNSUPPORTED, "Cartesian grid too large");
-            c->devCell.assign(g->ncells, 0);
-            for (int i = 0; i < g->nx; i++)
-                for (int j = 0; j < g->ny; j++)
-                    for (int k = 0; k < g->nz; k++)
-                        c->devCell[k + g->nz * j + g->nz * g->ny * i] =
-                            (int)((((i >> 1) * by + (j >> 1)) * bz + (k >> 1)) << 3) | ((i & 1) << 2) | ((j & 1) << 1) | (k & 1);
-            c->ndev = (int)(8 * bx * by * bz);
-        }
-        c->gx0 = g->xv[0]; c->gx1 = g->xv[g->nx];
-        c->gy0 = g->yv[0]; c->gy1 = g->yv[g->ny];
-        c->gz0 = g->zv[0]; c->gz1 = g->zv[g->nz];
-        int rc = upload(c, c->dMesh, mesh.data(), mesh.size());
-        if (rc) return rc;
-    } else if (g->kind == SKIRT_GRID_OCTREE) {
-        if (g->nnodes < 1 || !g->box || !g->first_child || !g->cellnumber || !g->nbr_offset)
-            return fail(c, SKIRT_ERR_ARG, "bad octree grid");
-        // validate the index arrays so that the kernels never read out of bounds
-        const bool bin = g->split_dir != nullptr;
-        const int arity = bin ? 2 : 8;
-        int nleaf = 0;
-        for (int l = 0; l < g->nnodes; l++) {
-            const int fc = g->first_child[l];
-            if (fc >= 0 && (fc + arity > g->nnodes || fc <= l)) return fail(c, SKIRT_ERR_ARG, "octree child index out of range");
-            if (fc >= 0 && bin && (g->split_dir[l] < 0 || g->split_dir[l] > 2)) return fail(c, SKIRT_ERR_ARG, "bad k-d tree split axis");
-            if (fc < 0) {
-                if (g->cellnumber[l] < 0 || g->cellnumber[l] >= g->ncells) return fail(c, SKIRT_ERR_ARG, "octree cell number out of range");
-                nleaf++;
-            }
-        }
-        if (nleaf != g->ncells) return fail(c, SKIRT_ERR_ARG, "octree leaf count != ncells");
-        const int nnbr = g->nbr_offset[6 * (size_t)g->nnodes];
-        for (size_t q = 0; q < 6 * (size_t)g->nnodes; q++)
-            if (g->nbr_offset[q] < 0 || g->nbr_offset[q] > g->nbr_offset[q + 1]) return fail(c, SKIRT_ERR_ARG, "bad neighbor offsets");
-        for (int q = 0; q < nnbr; q++)
-            if (g->nbr_list[q] < 0 || g->nbr_list[q] >= g->nnodes) return fail(c, SKIRT_ERR_ARG, "neighbor index out of range");
-        if (g->search < SKIRT_TREE_TOPDOWN || g->search > SKIRT_TREE_BOOKKEEPING) return fail(c, SKIRT_ERR_ARG, "bad tree search method");
-        std::vector<int> father;
-        if (g->search == SKIRT_TREE_BOOKKEEPING) {
-            // the Bookkeeping search reads octants off the breadth-first numbering: every group of
-            // children must start at an id = 1 (mod 8) (TreeDustGrid.cpp:525)
-            if (bin) return fail(c, SKIRT_ERR_ARG, "Bookkeeping method is not compatible with binary tree");
-            father.assign(g->nnodes, -1);
-            for (int l = 0; l < g->nnodes; l++) {
-                const int fc = g->first_child[l];
-                if (fc < 0) continue;
-                if ((fc - 1) % 8 != 0) return fail(c, SKIRT_ERR_ARG, "octree not numbered breadth-first for the Bookkeeping search");
-                for (int k = 0; k < 8; k++) father[fc + k] = l;
-            }
-        }
-        c->nnodes = g->nnodes;
-        c->eps = g->eps;
-        c->search = g->search;
-        c->gx0 = g->box[0]; c->gy0 = g->box[1]; c->gz0 = g->box[2];
-        c->gx1 = g->box[3]; c->gy1 = g->box[4]; c->gz1 = g->box[5];
-        int rc;
-        if ((rc = upload(c, c->dBox, g->box, 6 * (size_t)g->nnodes))) return rc;
-        if ((rc = upload(c, c->dFirstChild, g->first_child, (size_t)g->nnodes))) return rc;
-        c->binTree = bin;
-        if (!father.empty() && (rc = upload(c, c->dFather, father.data(), father.size()))) return rc;
-        if (bin) {
-            std::vector<signed char> dirs(g->split_dir, g->split_dir + g->nnodes);
-            for (int l = 0; l < g->nnodes; l++)
-                if (g->first_child[l] < 0) dirs[l] = 0;
-            if ((rc = upload(c, c->dSplitDir, dirs.data(), dirs.size()))) return rc;
-        }
-        // Morton order of the leaves: depth-first, children in octant order (x, y, z bits). A ray crosses
-        // about 2.5 of the 8 children of a node it enters, so 8 sibling leaves are numbered from a
-        // multiple of 8 (one 64-byte line of every Labs row), leaving unused device cells before them:
-        // the ray's Labs adds into them then share one atomic request (SKIRT_AMD_CELL_ALIGN=0: no gaps).
-        c->devCell.assign(g->ncells, -1);
-        {
-            const char* alignEnv = getenv("SKIRT_AMD_CELL_ALIGN");
-            const bool align = arity == 8 && !(alignEnv && alignEnv[0] == '0');
-            std::vector<int> stack{0};
-            int next = 0, used = 0;
-            auto number = [&](int l) -> bool {
-                if (c->devCell[g->cellnumber[l]] >= 0) return false;
-                c->devCell[g->cellnumber[l]] = next++;
-                used++;
-                return true;
-            };
-            while (!stack.empty()) {
-                const int l = stack.back();
-                stack.pop_back();
-                const int fc = g->first_child[l];
-                if (fc < 0) {
-                    if (!number(l)) return fail(c, SKIRT_ERR_ARG, "octree cell number used twice");
-                    continue;
-                }
-                bool leaves = align;
-                for (int k = 0; k < arity && leaves; k++) leaves = g->first_child[fc + k] < 0;
-                if (leaves) {  // the sibling leaves, aligned: the same depth-first order
-                    next = (next + 7) & ~7;
-                    for (int k = 0; k < arity; k++)
-                        if (!number(fc + k)) return fail(c, SKIRT_ERR_ARG, "octree cell number used twice");
-                } else {
-                    for (int k = arity - 1; k >= 0; k--) stack.push_back(fc + k);
-                }
-            }
-            if (used != g->ncells) return fail(c, SKIRT_ERR_ARG, "octree leaves do not cover the cells");
-            c->ndev = next;
-        }
-        std::vector<int> cellNode(g->ncells, 0);
-        for (int l = 0; l < g->nnodes; l++)
-            if (g->first_child[l] < 0) cellNode[g->cellnumber[l]] = l;
-        if ((rc = upload(c, c->dCellNode, cellNode.data(), cellNode.size()))) return rc;
-        std::vector<int> cn(g->cellnumber, g->cellnumber + g->nnodes);
-        for (int l = 0; l < g->nnodes; l++)
-            if (cn[l] >= 0) cn[l] = c->devCell[cn[l]];
-        if ((rc = upload(c, c->dCellnumber, cn.data(), (size_t)g->nnodes))) return rc;
-        if ((rc = upload(c, c->dNbrOffset, g->nbr_offset, 6 * (size_t)g->nnodes + 1))) return rc;
-        std::vector<int> dummy(1, 0);
-        if ((rc = upload(c, c->dNbrList, nnbr ? g->nbr_list : dummy.data(), nnbr ? (size_t)nnbr : 1))) return rc;
-        if ((rc = planLeafMap(c, g))) return rc;
-    } else if (g->kind == SKIRT_GRID_VORONOI) {
-        const int N = g->ncells;
-        if (N < 1 || !g->site || !g->cell_nbr_offset || !g->cell_nbr_list || !g->cell_bbox || g->nblocks < 1 ||
-            !g->block_offset || !g->block_list)
-            return fail(c, SKIRT_ERR_ARG, "bad Voronoi grid");
-        if (N > kCellMaskOut) return fail(c, SKIRT_ERR_UNSUPPORTED, "more than 2^28 Voronoi cells");
-        const int nnbr = g->cell_nbr_offset[N];
-        for (int m = 0; m < N; m++)
-            if (g->cell_nbr_offset[m] < 0 || g->cell_nbr_offset[m] > g->cell_nbr_offset[m + 1])
-                return fail(c, SKIRT_ERR_ARG, "bad Voronoi neighbour offsets");
-        for (int q = 0; q < nnbr; q++)
-            if (g->cell_nbr_list[q] < -6 || g->cell_nbr_list[q] >= N) return fail(c, SKIRT_ERR_ARG, "Voronoi neighbour out of range");
-        const size_t nb3 = (size_t)g->nblocks * g->nblocks * g->nblocks;
-        const int nbl = g->block_offset[nb3];
-        for (int q = 0; q < nbl; q++)
-            if (g->block_list[q] < 0 || g->block_list[q] >= N) return fail(c, SKIRT_ERR_ARG, "Voronoi block list out of range");
-        c->eps = g->eps;
-        c->gx0 = g->extent[0]; c->gy0 = g->extent[1]; c->gz0 = g->extent[2];
-        c->gx1 = g->extent[3]; c->gy1 = g->extent[4]; c->gz1 = g->extent[5];
-        c->vnb = g->nblocks;
-        // device cell numbers in Morton order of the sites (21 bits per axis, ties by reference number):
-        // cells adjacent in space are adjacent in memory, for the neighbour lists, the densities and the
-        // Labs tallies alike. Every list keeps its reference order (first-minimum choices depend on it).
-        c->devCell.assign(N, 0);
-        {
-            std::vector<std::pair<uint64_t, int>> key(N);
-            const double ext[3] = {c->gx1 - c->gx0, c->gy1 - c->gy0, c->gz1 - c->gz0};
-            const double lo[3] = {c->gx0, c->gy0, c->gz0};
-            for (int m = 0; m < N; m++) {
-                uint64_t code = 0;
-                for (int d = 0; d < 3; d++) {
-                    const double f = (g->site[3 * (size_t)m + d] - lo[d]) / ext[d];
-                    const uint64_t u = (uint64_t)std::max(0.0, std::min(2097151.0, f * 2097152.0));
-                    for (int bit = 0; bit < 21; bit++) code |= ((u >> bit) & 1ull) << (3 * bit + (2 - d));
-                }
-                key[m] = {code, m};
-            }
-            std::sort(key.begin(), key.end());
-            for (int q = 0; q < N; q++) c->devCell[key[q].second] = q;
-        }
-        std::vector<int> refOf(N);
-        for (int m = 0; m < N; m++) refOf[c->devCell[m]] = m;
-        std::vector<double> site(3 * (size_t)N), bbox(6 * (size_t)N);
-        // each device cell's block: kVorHead header slots + one slot per neighbour, in pairs (see VorEntry);
-        // the array is padded by kVorPad slots, since a step loads whole groups of entries
-        std::vector<int> start(N + 1, 0);
-        for (int d = 0; d < N; d++) {
-            const int m = refOf[d];
-            const int cnt = g->cell_nbr_offset[m + 1] - g->cell_nbr_offset[m];
-            if (cnt < 1) return fail(c, SKIRT_ERR_ARG, "Voronoi cell without neighbours");
-            // whole groups of kVorUnroll entries (even)
-            const int per = kVorUnroll;
-            start[d + 1] = start[d] + kVorHead + (cnt + per - 1) / per * per;
-        }
-        if ((size_t)start[N] + kVorPad >= (size_t)INT32_MAX) return fail(c, SKIRT_ERR_UNSUPPORTED, "Voronoi mesh too large");
-        std::vector<VorEntry> slots((size_t)start[N] + kVorPad, VorEntry{0.f, 0.f, 0.f, -1});
-        // offsets in units of the domain's largest half-width: single-precision squares stay in range
-        c->vorScale = 2.0 / std::max({c->gx1 - c->gx0, c->gy1 - c->gy0, c->gz1 - c->gz0});
-        for (int d = 0; d < N; d++) {
-            const int m = refOf[d];
-            const double* sm = g->site + 3 * (size_t)m;
-            for (int q = 0; q < 3; q++) site[3 * (size_t)d + q] = sm[q];
-            for (int q = 0; q < 6; q++) bbox[6 * (size_t)d + q] = g->cell_bbox[6 * (size_t)m + q];
-            VorEntry* blk = slots.data() + start[d];
-            const double head[4] = {sm[0], sm[1], sm[2], 0.0};  // rho of component 0: set by upload_media
-            std::memcpy(blk, head, sizeof head);
-            const int cnt = g->cell_nbr_offset[m + 1] - g->cell_nbr_offset[m];
-            std::vector<float> off(3 * (size_t)cnt);
-            int o = 0;
-            for (int q = g->cell_nbr_offset[m]; q < g->cell_nbr_offset[m + 1]; q++, o++) {
-                const int id = g->cell_nbr_list[q];
-                VorEntry e;
-                if (id < 0) {
-                    // a wall (-1 xmin, -2 xmax, ... -6 zmax) is the bisector plane of the site and its mirror
-                    // image: the offset to the mirror site along the wall's axis (NaN when the site lies on
-                    // the wall: the step then evaluates the list exactly)
-                    const int axis = (-id - 1) / 2;
-                    const double lim[6] = {c->gx0, c->gx1, c->gy0, c->gy1, c->gz0, c->gz1};
-                    const double w = lim[-id - 1] - sm[axis];
-                    double n[3] = {0.0, 0.0, 0.0};
-                    n[axis] = w != 0.0 ? 2.0 * w * c->vorScale : NAN;
-                    float o[3];
-                    vorRecipOffset(n[0], n[1], n[2], o);  // m = n / |n|^2 (vor_terms.hpp)
-                    e = VorEntry{o[0], o[1], o[2], id};
-                } else {
-                    const double* si = g->site + 3 * (size_t)id;
-                    float o[3];
-                    vorRecipOffset((si[0] - sm[0]) * c->vorScale, (si[1] - sm[1]) * c->vorScale,
-                                   (si[2] - sm[2]) * c->vorScale, o);
-                    e = VorEntry{o[0], o[1], o[2], start[c->devCell[id]]};
-                }
-                // entry o in its pair (see VorEntry): {ox0, ox1, oy0, oy1} {oz0, oz1, next0, next1}
-                float* P = reinterpret_cast<float*>(blk + kVorHead + (o & ~1));
-                const int h = o & 1;
-                P[h] = e.ox; P[2 + h] = e.oy; P[4 + h] = e.oz;
-                std::memcpy(P + 6 + h, &e.next, 4);
-                off[3 * (size_t)o] = e.ox; off[3 * (size_t)o + 1] = e.oy; off[3 * (size_t)o + 2] = e.oz;
-            }
-            // the padding up to the next block: NaN entries, no exit for any direction (bounds())
-            for (int q = cnt; q < start[d + 1] - start[d] - kVorHead; q++) {
-                float* P = reinterpret_cast<float*>(blk + kVorHead + (q & ~1));
-                const int h = q & 1;
-                P[h] = P[2 + h] = P[4 + h] = NAN;
-                const int none = -1;
-                std::memcpy(P + 6 + h, &none, 4);
-            }
-            // the header's last words: id, count and the cell's error terms of the bounds (vor_terms.hpp)
-            float eA, eB;
-            vorRecipErrorTerms(off.data(), cnt, 3, &eA, &eB);
-            int ids[4] = {d, cnt, 0, 0};
-            std::memcpy(&ids[2], &eA, 4);
-            std::memcpy(&ids[3], &eB, 4);
-            std::memcpy(blk + 2, ids, sizeof ids);
-        }
-        c->vorSlotsHost = std::move(slots);
-        std::vector<BlockSite> blocks(std::max(nbl, 1), BlockSite{0.0, 0.0, 0.0, -1, 0});
-        for (int q = 0; q < nbl; q++) {
-            const int m = g->block_list[q];
-            blocks[q] = BlockSite{g->site[3 * (size_t)m], g->site[3 * (size_t)m + 1], g->site[3 * (size_t)m + 2], c->devCell[m], 0};
-        }
-        int rc;
-        if ((rc = upload(c, c->dSite, site.data(), site.size()))) return rc;
-        if ((rc = upload(c, c->dCellBbox, bbox.data(), bbox.size()))) return rc;
-        if ((rc = upload(c, c->dVorStart, start.data(), start.size()))) return rc;
-        if ((rc = upload(c, c->dVorSlots, c->vorSlotsHost.data(), c->vorSlotsHost.size()))) return rc;
-        c->vorStartHost = std::move(start);
-        if ((rc = upload(c, c->dBlockOffset, g->block_offset, nb3 + 1))) return rc;
-        if ((rc = upload(c, c->dBlockSites, blocks.data(), blocks.size()))) return rc;
-        if ((rc = upload(c, c->dDevCell, c->devCell.data(), c->devCell.size()))) return rc;
-    } else if (g->kind == SKIRT_GRID_CYLINDER2D) {
-        if (g->nx < 1 || g->nz < 1 || !g->xv || !g->zv) return fail(c, SKIRT_ERR_ARG, "bad cylindrical grid");
-        if ((long long)g->nx * g->nz != g->ncells) return fail(c, SKIRT_ERR_ARG, "ncells != nx*nz");
-        if (g->xv[0] != 0.0) return fail(c, SKIRT_ERR_ARG, "the radial mesh does not start at 0");
-        for (int i = 0; i < g->nx; i++) if (!(g->xv[i] < g->xv[i + 1])) return fail(c, SKIRT_ERR_ARG, "R mesh not increasing");
-        for (int i = 0; i < g->nz; i++) if (!(g->zv[i] < g->zv[i + 1])) return fail(c, SKIRT_ERR_ARG, "z mesh not increasing");
-        // R | one unused word | z: the Cartesian mesh layout with ny = 0
-        std::vector<double> mesh;
-        mesh.insert(mesh.end(), g->xv, g->xv + g->nx + 1);
-        mesh.push_back(0.0);
-        mesh.insert(mesh.end(), g->zv, g->zv + g->nz + 1);
-        c->nx = g->nx; c->ny = 0; c->nz = g->nz;
-        c->gx0 = -g->xv[g->nx]; c->gx1 = g->xv[g->nx];
-        c->gy0 = -g->xv[g->nx]; c->gy1 = g->xv[g->nx];
-        c->gz0 = g->zv[0]; c->gz1 = g->zv[g->nz];
-        c->mapL = -1;
-        int rc = upload(c, c->dMesh, mesh.data(), mesh.size());
-        if (rc) return rc;
-    } else if (g->kind == SKIRT_GRID_SPHERE1D || g->kind == SKIRT_GRID_SPHERE2D) {
-        const bool two = g->kind == SKIRT_GRID_SPHERE2D;
-        const int nt = two ? g->nz : 0;
-        if (g->nx < 1 || !g->xv) return fail(c, SKIRT_ERR_ARG, "bad spherical grid");
-        if (two ? (nt < 1 || g->ny != nt || !g->yv || !g->zv) : (g->ny != 0 || g->nz != 0))
-            return fail(c, SKIRT_ERR_ARG, "bad spherical grid");
-        if ((long long)g->nx * (two ? nt : 1) != g->ncells) return fail(c, SKIRT_ERR_ARG, "ncells != nx*nz");
-        const double rmax = g->extent[3];
-        if (!(rmax > 0.0) || !(g->xv[g->nx - 1] < rmax)) return fail(c, SKIRT_ERR_ARG, "extent does not hold the outer radius");
-        if (g->xv[0] != 0.0) return fail(c, SKIRT_ERR_ARG, "the radial mesh does not start at 0");
-        for (int i = 0; i < g->nx; i++) if (!(g->xv[i] < g->xv[i + 1])) return fail(c, SKIRT_ERR_ARG, "r mesh not increasing");
-        for (int i = 0; i < nt; i++) if (!(g->zv[i] < g->zv[i + 1])) return fail(c, SKIRT_ERR_ARG, "theta mesh not increasing");
-        for (int i = 0; i < nt; i++) if (!(g->yv[i] > g->yv[i + 1])) return fail(c, SKIRT_ERR_ARG, "cosines not decreasing");
-        if (two && !(g->eps > 0.0)) return fail(c, SKIRT_ERR_ARG, "eps should be positive");
-        // r | cos theta | theta: the Cartesian mesh layout (one unused word each where ny = nz = 0)
-        std::vector<double> mesh;
-        mesh.insert(mesh.end(), g->xv, g->xv + g->nx + 1);
-        if (two) {
-            mesh.insert(mesh.end(), g->yv, g->yv + nt + 1);
-            mesh.insert(mesh.end(), g->zv, g->zv + nt + 1);
-        } else {
-            mesh.push_back(0.0);
-            mesh.push_back(0.0);
-        }
-        c->nx = g->nx; c->ny = nt; c->nz = nt;
-        c->gx0 = -rmax; c->gx1 = rmax;
-        c->gy0 = -rmax; c->gy1 = rmax;
-        c->gz0 = -rmax; c->gz1 = rmax;
-        c->eps = two ? g->eps : 0.0;
-        c->mapL = -1;
-        int rc = upload(c, c->dMesh, mesh.data(), mesh.size());
-        if (rc) return rc;
-    } else {
-        return fail(c, SKIRT_ERR_UNSUPPORTED, "unsupported grid kind");
+    c->mapL = -1;
+    c->mapReady = false;
+    c->binTree = false;
+    int rc;
+    switch (g->kind) {
+    case SKIRT_GRID_CARTESIAN: rc = uploadCartesian(c, g); break;
+    case SKIRT_GRID_OCTREE: rc = uploadTree(c, g); break;
+    case SKIRT_GRID_VORONOI: rc = uploadVoronoi(c, g); break;
+    case SKIRT_GRID_CYLINDER2D: rc = uploadCylinder(c, g); break;
+    case SKIRT_GRID_SPHERE1D:
+    case SKIRT_GRID_SPHERE2D: rc = uploadSphere(c, g); break;
+    default: return fail(c, SKIRT_ERR_UNSUPPORTED, "unsupported grid kind");
     }
+    if (rc) return rc;
     c->labsStride = (c->ndev + 7) & ~7;
     c->gridKind = g->kind;
     return SKIRT_OK;
@@ -4521,6 +4555,345 @@ static int phaseEndReduce(SkirtMcrt* c, int phase, const SkirtPhaseParams* p) {
     return r ? fail(c, SKIRT_ERR_STATE, "the absorption reduction failed") : SKIRT_OK;
 }
 
+// What one phase runs with: everything the iteration loop needs that does not change between iterations.
+struct PhasePlan {
+    Args a{};  // the kernel arguments, but for the pool (carvePool) and the per-iteration parity, init and det
+    int kind = kOctreeNodes;  // the grid walk (kWalks)
+    bool continuous = false, noStore = false, detAside = false;
+    size_t ldsTrace = 0, ldsEvent = 0, ldsDetect = 0;  // dynamic LDS of the trace, event / continuous and detect kernels
+    const void* traceFn = nullptr;
+    int tgrid = 0, egrid = 0, dgrid = 0;  // workgroups of the trace, event / continuous and detect launches
+    double* labsTarget = nullptr;  // the Labs replicas (a.labsCopies > 1) fold into this table of labsElems elements
+    uint64_t labsElems = 0;
+};
+
+static int envInt(const char* name, int dflt) {
+    const char* s = getenv(name);
+    return s ? atoi(s) : dflt;
+}
+
+// the plan's Labs addressing mode and replicas (a.store is set; fills a.labs*)
+static int planLabs(SkirtMcrt* c, int phase, PhasePlan& pl) {
+    Args& a = pl.a;
+    // the trace kernel adds to Labs through a buffer descriptor (32-bit byte offsets, one byte past the end
+    // for the drain's empty lanes) while the table holds at most 4 GiB - 8 (e.g. 2^21 cells x 255
+    // wavelengths), with global atomics beyond (SKIRT_AMD_LABS_GLOBAL=1 forces them: tests)
+    const uint64_t labsElems = pl.labsElems = (uint64_t)c->labsStride * (uint64_t)c->nlambda;
+    // 2^32 elements or more (32 GiB): the buffered adds carry 40-bit element indices (SKIRT_AMD_LABS_HI=1 forces
+    // that path: tests); 2^40 elements at most
+    if (a.store && labsElems >= (1ull << 40)) return fail(c, SKIRT_ERR_UNSUPPORTED, "Labs table of 2^40 elements or more");
+    const bool forceHi = envInt("SKIRT_AMD_LABS_HI", 0) != 0;
+    a.labsHi = (a.store && (forceHi || labsElems > 0xffffffffull)) ? 1 : 0;
+    const bool forceGlobal = envInt("SKIRT_AMD_LABS_GLOBAL", 0) != 0;
+    a.labsGlobal = (forceGlobal || a.labsHi || labsElems * sizeof(double) > 0xfffffff8ull) ? 1 : 0;
+    a.labs = phase == SKIRT_PHASE_DUST_SELFABS ? c->dLabsDust : c->dLabs;
+    a.labsBytes = a.labsGlobal ? 0u : (unsigned)(labsElems * sizeof(double));
+    // The trace waves add into K replicas of the table (wave w into w % K), folded into it at the phase end:
+    // the adds to one cell spread over K lines, which the memory-side atomic unit works on side by side.
+    // In the stellar phase the replicas pay while they stay near the MALL (256 MB): C3 (a 129 MB table) 2:
+    // +1.1 %, 3: +1.2 %, 4: +0.8 %, 6: -1 %, 8: -3.4 %; C2 (21 MB) 4: +2 %, 8: +3.3 %. The self-absorption
+    // cycles' adds crowd onto fewer lines and gain up to 6: C5 with 3 in the stellar phase and 6 in the
+    // cycles +9.0 % against none, +3.6 % against 2 everywhere; C3 +1.2 % (profiles/r05_labs_copies_ab.txt).
+    // K = 400 MiB (self-absorption: 800 MiB) / the table, at most 8; SKIRT_AMD_LABS_COPIES sets it (1: none)
+    pl.labsTarget = a.labs;
+    a.labsCopies = 1;
+    a.labsCopyStride = 0;
+    const uint64_t tableBytes = (uint64_t)a.labsBytes > 0 ? (uint64_t)a.labsBytes : 1;
+    const uint64_t budget = phase == SKIRT_PHASE_DUST_SELFABS ? (800ull << 20) : (400ull << 20);
+    const int Kauto = (int)std::min<uint64_t>(8, std::max<uint64_t>(1, budget / tableBytes));
+    const int K = envInt("SKIRT_AMD_LABS_COPIES", Kauto);
+    const uint64_t stride = ((uint64_t)a.labsBytes + 255) & ~255ull;
+    if (a.store && !a.labsGlobal && K > 1 && K <= 64 && stride * (uint64_t)K <= 0xfffffff0ull) {
+        const size_t need = (size_t)stride * K;
+        if (c->labsRepBytes < need) {
+            if (c->dLabsRep) HIPCHECK(c, hipFree(c->dLabsRep));
+            c->dLabsRep = nullptr;
+            c->labsRepBytes = 0;
+            HIPCHECK(c, hipMalloc(&c->dLabsRep, need));
+            HIPCHECK(c, hipMemsetAsync(c->dLabsRep, 0, need, c->stream));
+            c->labsRepBytes = need;
+        }
+        if (c->labsRepDirty) {  // (the failed phase's kernels may still run, on sD too)
+            HIPCHECK(c, hipDeviceSynchronize());
+            HIPCHECK(c, hipMemsetAsync(c->dLabsRep, 0, c->labsRepBytes, c->stream));
+        }
+        c->labsRepDirty = true;  // until the fold at this phase's end
+        a.labs = c->dLabsRep;
+        a.labsCopies = K;
+        a.labsCopyStride = (unsigned)stride;
+    }
+    return SKIRT_OK;
+}
+
+// the plan's LDS layout (a.lds*Off, a.detCopies), LDS sizes and the no-store choice
+static int planLds(SkirtMcrt* c, PhasePlan& pl) {
+    Args& a = pl.a;
+    // LDS layout (doubles): mesh | optics | instruments | SED sums
+    int off = 0;
+    a.ldsMeshOff = off;
+    off += (walkOf(pl.kind).meshInLds && a.hasDust) ? (c->nx + c->ny + c->nz + 3) : 0;
+    off += a.leafMap ? 3 * (c->mapN + 1) : 0;
+    off = (off + 1) & ~1;
+    a.ldsOptOff = off;
+    off += 4 * a.ncomp * a.nlambda;
+    off = (off + 1) & ~1;
+    a.ldsInstrOff = off;
+    off += a.ninstr * (int)(sizeof(DevInstr) / sizeof(double));
+    a.ldsSedOff = off;
+    off += c->nsed;
+    // a phase storing no absorption with one component runs traceKernelNoStore (no Labs buffers)
+    const bool noStore = pl.noStore = !a.store && a.ncomp == 1 && !pl.continuous && c->gridKind != SKIRT_GRID_VORONOI &&
+                         !getenv("SKIRT_AMD_NO_NOSTORE");
+    const size_t ldsTrace = pl.ldsTrace = (size_t)a.ldsInstrOff * sizeof(double)          // grid tables + optics
+                            + (size_t)kSegWords * sizeof(double)                          // + segment counts
+                            + (noStore ? 0 : (size_t)kLabsBuf * kBlock * (sizeof(double) + sizeof(unsigned)))  // + Labs buffers
+                            + (a.labsHi ? (size_t)kLabsBuf * kBlock : 0);  // + their high index bytes
+    const size_t ldsEvent = pl.ldsEvent = (size_t)a.ldsSedOff * sizeof(double);           // + instruments
+    // budget: what one workgroup may allocate (160 KiB on gfx950). The trace and event kernels need their
+    // tables; the detect kernel keeps as many SED copies as fit (8, 4, 2, 1), or none (SEDs to the tally)
+    const size_t budget = c->ldsMax;
+    if (ldsTrace > budget || ldsEvent > budget)
+        return fail(c, SKIRT_ERR_UNSUPPORTED, "grid and optical tables do not fit in LDS (" +
+                                                  std::to_string(std::max(ldsTrace, ldsEvent)) + " of " +
+                                                  std::to_string(budget) + " bytes)");
+    // SKIRT_AMD_DET_COPIES caps the copies (tests of the fallbacks)
+    const int capCopies = envInt("SKIRT_AMD_DET_COPIES", kDetectCopies);
+    a.detCopies = kDetectCopies;
+    while (a.detCopies > 0 && a.detCopies > capCopies) a.detCopies >>= 1;
+    while (a.detCopies > 0 && ldsEvent + (size_t)a.detCopies * c->nsed * sizeof(double) > budget) a.detCopies >>= 1;
+    pl.ldsDetect = ldsEvent + (size_t)a.detCopies * c->nsed * sizeof(double);
+    c->lastDetCopies = a.detCopies;
+    // launches above 64 KiB of dynamic LDS declare it first
+    if (pl.ldsDetect > 64 * 1024)
+        HIPCHECK(c, hipFuncSetAttribute((const void*)detectKernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)pl.ldsDetect));
+    return SKIRT_OK;
+}
+
+// Fills the plan of a phase over the packets [first, first + count). What the plan's values depend on is made
+// ready on the way, in the order the phase has always issued these calls: the pool and the detect stream are
+// allocated, ensureLeafMap launches buildLeafMapKernel on the caller's stream, planLabs allocates and clears
+// the Labs replicas (hipMemsetAsync, after a failed phase behind a hipDeviceSynchronize), and planLds and this
+// function declare LDS above 64 KiB (hipFuncSetAttribute) and ask for the trace kernel's occupancy.
+static int planPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint64_t first, uint64_t count,
+                     uint64_t sliceLo, uint64_t sliceCnt, uint64_t seed, const SkirtPhaseParams* p, PhasePlan& pl) {
+    int rc;
+    // slot pool: enough packets in flight to fill the chip many times over, bounded by the phase size.
+    // 2^24 slots (6.6 GB of packet state and ray queues with one instrument) make each iteration's trace
+    // launch long enough that its drain tail and the event kernel amortise (round 1, C3: 2^21 slots 1.87e8
+    // pkt/s, 2^22 1.98e8, 2^23 2.04e8, 2^24 2.05e8; round 4 at the configurations' sizes, 2^24 against
+    // 2^23: C3 +1.5 %, C2 +0.7 %, C4 +0.7 %, C5 +0.3 %, profiles/r04_slots_2e24.txt)
+    int slots = c->slotsWanted > 0 ? c->slotsWanted : (1 << 24);
+    // continuous scattering (MonteCarloSimulation::continuousScattering): peel-offs from every dust segment
+    // of every path replace the ones at the interaction points; fewer slots, each with a longer queue
+    const bool continuous = pl.continuous = p->continuous_scattering && phase != SKIRT_PHASE_DUST_SELFABS && p->has_dust &&
+                            !c->instr.empty();
+    // (the queue holds kPathCap peel-offs per instrument and slot: the slots shrink with the instruments)
+    if (continuous) slots = std::min(slots, std::max(64, kContSlots / std::max(1, (int)c->instr.size())));
+    if ((uint64_t)slots > count) slots = (int)count;
+    // (a phase that fits the pool runs its packets in lockstep; admitting them in 2 or 4 waves instead changes
+    // neither the C5 step nor its 164 trace launches: the tail iterations are the few long-lived packets either
+    // way, profiles/r06_ab.txt)
+    slots = std::max(slots, 64);
+    // the detect kernel of an iteration beside the next iteration's event kernel (peel-offs at the
+    // interaction points): C3 +1.9 %, C2 within the spread; beside the next trace kernel as well, C3 +1.6 %,
+    // C2 -1.5 %. Not for Voronoi grids: C4 -2.2 %, and -2.6 % again after the counter-line and event-grid
+    // changes (profiles/r05_detect_aside_ab.txt)
+    pl.detAside = !continuous && !c->instr.empty() && p->has_dust && c->gridKind != SKIRT_GRID_VORONOI;
+    if ((rc = ensurePool(c, slots, continuous, pl.detAside))) return rc;
+    if (pl.detAside && !c->sD) {
+        HIPCHECK(c, hipStreamCreateWithFlags(&c->sD, hipStreamNonBlocking));
+        HIPCHECK(c, hipEventCreateWithFlags(&c->evDetT, hipEventDisableTiming));
+        HIPCHECK(c, hipEventCreateWithFlags(&c->evDet[0], hipEventDisableTiming));
+        HIPCHECK(c, hipEventCreateWithFlags(&c->evDet[1], hipEventDisableTiming));
+        HIPCHECK(c, hipEventCreateWithFlags(&c->evDetJoin, hipEventDisableTiming));
+    }
+    Args& a = pl.a;
+    gridArgs(c, a);
+    const int kind = pl.kind = walkKind(c, p->has_dust);
+    if (kind == SKIRT_GRID_OCTREE || kind == kBinTreeMap) {  // the leaf-map walks
+        if ((rc = ensureLeafMap(c))) return rc;
+        a.leafMap = c->dLeafMap; a.treeT = c->dTreeT; a.mapL = c->mapL; a.mapN = c->mapN;
+        a.mapInvX = c->mapInv[0]; a.mapInvY = c->mapInv[1]; a.mapInvZ = c->mapInv[2];
+        a.mapX0 = c->mapOrigin[0]; a.mapY0 = c->mapOrigin[1]; a.mapZ0 = c->mapOrigin[2];
+    }
+    a.optics = c->dOptics;
+    a.nstar = c->nstar; a.geomParam = c->dGeomParam; a.geomTable = c->dGeomTable; a.lum = c->dLum;
+    a.lumtot = c->dLumtot; a.cdf = c->dCdf; a.emissionBias = c->emissionBias;
+    a.ninstr = (int)c->instr.size(); a.instr = c->dInstr; a.nsed = c->nsed;
+    a.npp = npp; a.first = first; a.end = first + count; a.seed = seed;
+    a.sliceLo = sliceLo; a.sliceCnt = sliceCnt;
+    a.tag = (unsigned)phase | (cycle << 2);  // Philox counter word 1: streams differ per phase and cycle
+    a.phase = phase;
+    a.peel = phase != SKIRT_PHASE_DUST_SELFABS;
+    a.continuous = continuous ? 1 : 0;
+    a.cellLv = c->dCellLv; a.cellCdf = c->dCellCdf; a.cellGuide = c->dCellGuide; a.cellLtot = c->dCellLtot; a.cellBias = c->cellBias;
+    a.cellNode = c->dCellNode;
+    a.minWeightReduction = p->min_weight_reduction; a.minScatt = p->min_scatt_events; a.xi = p->scatt_bias;
+    // absorption: the stellar phase as its parameters say (into Labs), self-absorption always (into the
+    // dust Labs), dust emission never (MonteCarloSimulation.cpp:287, PanMonteCarloSimulation.cpp:223, 331)
+    a.store = phase == SKIRT_PHASE_STELLAR ? (p->store_absorption ? 1 : 0) : (phase == SKIRT_PHASE_DUST_SELFABS ? 1 : 0);
+    a.hasDust = p->has_dust ? 1 : 0;
+    if (a.store && !c->dLabs) return fail(c, SKIRT_ERR_STATE, "no Labs buffer");
+    if ((rc = planLabs(c, phase, pl))) return rc;
+    a.tally = c->dTally;
+    a.error = c->dError; a.stats = c->dStats;
+    a.crossed = c->dCrossed; a.crossedBins = c->crossedBins;
+    a.claim = c->dClaim;
+    a.threshold = c->threshold > 0 ? c->threshold : (c->gridKind == SKIRT_GRID_VORONOI ? 8 : 16);
+    a.walkBack = c->walkBack >= 0 ? c->walkBack : (c->gridKind == SKIRT_GRID_VORONOI ? 1 : 0);
+    if ((rc = planLds(c, pl))) return rc;
+    c->lastWalk = walkOf(kind).stat;
+    pl.traceFn = traceKernelOf(kind, a.ncomp == 1, continuous, a.labsGlobal != 0, pl.noStore);
+    if (pl.ldsTrace > 64 * 1024)
+        HIPCHECK(c, hipFuncSetAttribute(pl.traceFn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.ldsTrace));
+    pl.tgrid = c->traceGrid;
+    if (pl.tgrid <= 0) {
+        int per = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, pl.traceFn, kBlock, pl.ldsTrace) != hipSuccess || per < 1) per = 2;
+        pl.tgrid = std::max(1, c->numCUs) * per;
+        c->traceBlocksPerCU = per;
+    }
+    // event kernel blocks per CU: 3 (3 waves/SIMD, the registers allow it). Voronoi: C4 +0.6 % against 2
+    // (profiles/r04_event_bpc_sweep.txt); the other grids, once the block reservations no longer serialize on
+    // one counter line: C3 +0.7 %, C2 +2.3 % against 2, 4 the same as 3 (profiles/r05_event_bpc_ab.txt)
+#ifndef SKIRT_EVENT_BPC
+#define SKIRT_EVENT_BPC 3
+#endif
+    const int ebpc = SKIRT_EVENT_BPC;
+    pl.egrid = std::max(1, std::min((slots + kBlock - 1) / kBlock, std::max(1, c->numCUs) * ebpc));
+    pl.dgrid = std::max(1, std::max(1, c->numCUs) * 4);
+    return SKIRT_OK;
+}
+
+// Iteration it (parity q = it & 1): the event kernel consumes active list ctr[2+q] and queues rays
+// into ctr[q] and the next active list into ctr[2+1-q]; the trace kernel walks the ctr[q] rays and
+// resets ctr[1-q] and ctr[2+q] for the next iteration; the detect kernel turns the finished peel-off
+// rays into detections. After every detect kernel the counters are copied to pinned memory behind an
+// event; the host reads each copy kPollRing copies later (by then long complete), so it never drains
+// the stream. Once an active count was 0 the phase is finished; the few iterations launched after
+// that point find no work and exit at once.
+static int runIterations(SkirtMcrt* c, const PhasePlan& pl) {
+    const int kind = pl.kind;
+    const bool one = pl.a.ncomp == 1;
+    auto launchEvent = [&](const Args& aa, hipStream_t st) {
+        withWalk(kind, [&](auto g) {
+            withBool(one, [&](auto o) {
+                hipLaunchKernelGGL((eventKernel<decltype(g)::value, decltype(o)::value>), dim3(pl.egrid), dim3(kBlock),
+                                   pl.ldsEvent, st, aa);
+            });
+        });
+    };
+    auto launchCont = [&](const Args& aa, hipStream_t st) {
+        withWalk(kind, [&](auto g) {
+            withBool(one, [&](auto o) {
+                hipLaunchKernelGGL((contKernel<decltype(g)::value, decltype(o)::value>), dim3(pl.egrid), dim3(kBlock),
+                                   pl.ldsEvent, st, aa);
+            });
+        });
+    };
+    auto launchTrace = [&](const Args& aa, hipStream_t st) {
+        // the kernel of the plan (traceFn), launched through its generic entry
+        void* args[] = {const_cast<Args*>(&aa)};
+        return hipLaunchKernel(pl.traceFn, dim3(pl.tgrid), dim3(kBlock), args, pl.ldsTrace, st);
+    };
+    while ((int)c->pollEv.size() < kPollRing) {
+        hipEvent_t e;
+        HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->pollEv.push_back(e);
+    }
+    hipStream_t st = c->stream;
+    Args aa = pl.a, prev;
+    carvePool(c, aa);
+    DetRec* const detBase = aa.det;
+    int rc, its = 0, polls = 0;
+    int pollIt[kPollRing] = {};  // the iteration count each copy was taken at
+    bool pendingDet = false;
+    // the detect kernel of the last trace launch (after that launch), then the counter copy.
+    // With detAside it runs on sD after the trace launch; the next iteration of the same parity, which
+    // writes that region of detection records again, waits for it (evDet). Its record count is then
+    // zeroed for that iteration's event kernel to append to.
+    bool detUsed[2] = {false, false};
+    auto detect = [&]() -> int {
+        pendingDet = false;
+        const Args& d = prev;
+        hipStream_t sd = pl.detAside ? c->sD : st;
+        if (pl.detAside) {
+            HIPCHECK(c, hipEventRecord(c->evDetT, st));
+            HIPCHECK(c, hipStreamWaitEvent(sd, c->evDetT, 0));
+        }
+        hipLaunchKernelGGL(detectKernel, dim3(pl.dgrid), dim3(kBlock), pl.ldsDetect, sd, d);
+        HIPCHECK(c, hipGetLastError());
+        HIPCHECK(c, hipMemsetAsync(CTRP(d.ctr, 5 + d.parity), 0, sizeof(unsigned int), sd));
+        if (pl.detAside) {
+            HIPCHECK(c, hipEventRecord(c->evDet[d.parity], sd));
+            detUsed[d.parity] = true;
+        }
+        return SKIRT_OK;
+    };
+    // iterations before the phase is declared stuck; SKIRT_AMD_MAX_ITERATIONS lowers the cap (tests of the
+    // error exits)
+    const int maxIts = envInt("SKIRT_AMD_MAX_ITERATIONS", 10000000);
+    int total = 0;
+    while (true) {
+        if (pendingDet && (rc = detect())) return rc;
+        if (its > 0 && its % kPollEvery == 0) {
+            const int slot = polls % kPollRing;
+            unsigned int* hc = c->hCtr + slot * kCtrWords;
+            hipEvent_t pe = c->pollEv[slot];
+            if (polls >= kPollRing) {
+                // the copy made kPollRing polls ago: is the phase finished?
+                HIPCHECK(c, hipEventSynchronize(pe));
+                if (CTR(hc, 2 + (pollIt[slot] & 1)) == 0) break;
+            }
+            HIPCHECK(c, hipMemcpyAsync(hc, aa.ctr, 8 * kCtrStride * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+            HIPCHECK(c, hipEventRecord(pe, st));
+            pollIt[slot] = its;
+            polls++;
+        }
+        if (its > maxIts) return fail(c, SKIRT_ERR_STATE, "photon phase did not terminate");
+        aa.parity = its & 1;
+        aa.init = (its == 0) ? 1 : 0;
+        if (pl.detAside) {
+            // this iteration's detection records: the region of its parity, free once the detect kernel of
+            // the last iteration of that parity is done
+            aa.det = detBase + (size_t)aa.parity * (size_t)(c->rayCap - c->nslots);
+            if (detUsed[aa.parity]) HIPCHECK(c, hipStreamWaitEvent(st, c->evDet[aa.parity], 0));
+        }
+        if (aa.continuous && !aa.init) {  // the continuous peel-offs of the FILL rays that just returned
+            launchCont(aa, st);
+            HIPCHECK(c, hipGetLastError());
+        }
+        launchEvent(aa, st);
+        HIPCHECK(c, hipGetLastError());
+        if (!aa.hasDust) break;  // every packet completes in the event kernel
+        if ((int)c->traceEv.size() < 2 * (c->traceLaunches + 1)) {
+            hipEvent_t e0, e1;
+            HIPCHECK(c, hipEventCreate(&e0));
+            HIPCHECK(c, hipEventCreate(&e1));
+            c->traceEv.push_back(e0);
+            c->traceEv.push_back(e1);
+        }
+        // the detect kernel of the last iteration runs beside this iteration's event kernel only
+        if (pl.detAside && detUsed[1 - aa.parity]) HIPCHECK(c, hipStreamWaitEvent(st, c->evDet[1 - aa.parity], 0));
+        HIPCHECK(c, hipEventRecord(c->traceEv[2 * c->traceLaunches], st));
+        HIPCHECK(c, launchTrace(aa, st));
+        HIPCHECK(c, hipGetLastError());
+        HIPCHECK(c, hipEventRecord(c->traceEv[2 * c->traceLaunches + 1], st));
+        c->traceLaunches++;
+        if (aa.ninstr > 0) { prev = aa; pendingDet = true; }
+        its++;
+        total++;
+    }
+    if (pendingDet && (rc = detect())) return rc;
+    c->lastIterations = total;
+    if (pl.detAside && (detUsed[0] || detUsed[1])) {  // the caller's stream continues after the last detect kernel
+        HIPCHECK(c, hipEventRecord(c->evDetJoin, c->sD));
+        HIPCHECK(c, hipStreamWaitEvent(c->stream, c->evDetJoin, 0));
+    }
+    return SKIRT_OK;
+}
+
 static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint64_t first, uint64_t count,
                     uint64_t sliceLo, uint64_t sliceCnt, uint64_t seed, const SkirtPhaseParams* p) {
     if (phase < SKIRT_PHASE_STELLAR || phase > SKIRT_PHASE_DUST_SELFABS) return fail(c, SKIRT_ERR_ARG, "unknown phase");
@@ -4562,408 +4935,15 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
         std::vector<double> z(4 * (size_t)c->nlambda, 0.0);
         if ((rc = upload(c, c->dOptics, z.data(), z.size()))) return rc;
     }
-    // slot pool: enough packets in flight to fill the chip many times over, bounded by the phase size.
-    // 2^24 slots (6.6 GB of packet state and ray queues with one instrument) make each iteration's trace
-    // launch long enough that its drain tail and the event kernel amortise (round 1, C3: 2^21 slots 1.87e8
-    // pkt/s, 2^22 1.98e8, 2^23 2.04e8, 2^24 2.05e8; round 4 at the configurations' sizes, 2^24 against
-    // 2^23: C3 +1.5 %, C2 +0.7 %, C4 +0.7 %, C5 +0.3 %, profiles/r04_slots_2e24.txt)
-    int slots = c->slotsWanted > 0 ? c->slotsWanted : (1 << 24);
-    // continuous scattering (MonteCarloSimulation::continuousScattering): peel-offs from every dust segment
-    // of every path replace the ones at the interaction points; fewer slots, each with a longer queue
-    const bool continuous = p->continuous_scattering && phase != SKIRT_PHASE_DUST_SELFABS && p->has_dust &&
-                            !c->instr.empty();
-    // (the queue holds kPathCap peel-offs per instrument and slot: the slots shrink with the instruments)
-    if (continuous) slots = std::min(slots, std::max(64, kContSlots / std::max(1, (int)c->instr.size())));
-    if ((uint64_t)slots > count) slots = (int)count;
-    // (a phase that fits the pool runs its packets in lockstep; admitting them in 2 or 4 waves instead changes
-    // neither the C5 step nor its 164 trace launches: the tail iterations are the few long-lived packets either
-    // way, profiles/r06_ab.txt)
-    const int halves = (continuous || !p->has_dust || slots < 2 * 64 * kMaxHalves) ? 1 : c->halves;
-    slots = std::max(slots, 64 * halves) / halves;  // per half
-    const bool forked = c->halves > 1 || c->cusT || c->cusE;  // the pipeline runs on the owned streams
-    // the detect kernel of an iteration beside the next iteration's event kernel (one pipeline on the
-    // caller's stream, peel-offs at the interaction points): C3 +1.9 %, C2 within the spread; beside the
-    // next trace kernel as well, C3 +1.6 %, C2 -1.5 %. Not for Voronoi grids: C4 -2.2 %, and -2.6 % again
-    // after the counter-line and event-grid changes (profiles/r05_detect_aside_ab.txt)
-    const bool detAside = !forked && !continuous && !c->instr.empty() && p->has_dust &&
-                          c->gridKind != SKIRT_GRID_VORONOI;
-    if ((rc = ensurePool(c, slots, continuous, halves, detAside))) return rc;
-    if ((rc = ensureStreams(c))) return rc;
-    if (detAside && !c->sD) {
-        HIPCHECK(c, hipStreamCreateWithFlags(&c->sD, hipStreamNonBlocking));
-        HIPCHECK(c, hipEventCreateWithFlags(&c->evDetT, hipEventDisableTiming));
-        HIPCHECK(c, hipEventCreateWithFlags(&c->evDet[0], hipEventDisableTiming));
-        HIPCHECK(c, hipEventCreateWithFlags(&c->evDet[1], hipEventDisableTiming));
-        HIPCHECK(c, hipEventCreateWithFlags(&c->evDetJoin, hipEventDisableTiming));
-    }
-    hipStream_t sE = forked ? c->sE : c->stream;
-    hipStream_t sT[kMaxHalves];
-    for (int h = 0; h < kMaxHalves; h++) sT[h] = forked ? c->sT[h] : c->stream;
-
-    Args a{};
-    gridArgs(c, a);
-    const bool bookkeeping = c->gridKind == SKIRT_GRID_OCTREE && c->search == SKIRT_TREE_BOOKKEEPING;
-    const bool leafMap = c->gridKind == SKIRT_GRID_OCTREE && c->mapL >= 0 && p->has_dust && !bookkeeping;
-    if (leafMap) {
-        if ((rc = ensureLeafMap(c))) return rc;
-        a.leafMap = c->dLeafMap; a.treeT = c->dTreeT; a.mapL = c->mapL; a.mapN = c->mapN;
-        a.mapInvX = c->mapInv[0]; a.mapInvY = c->mapInv[1]; a.mapInvZ = c->mapInv[2];
-        a.mapX0 = c->mapOrigin[0]; a.mapY0 = c->mapOrigin[1]; a.mapZ0 = c->mapOrigin[2];
-    }
-    a.optics = c->dOptics;
-    a.nstar = c->nstar; a.geomParam = c->dGeomParam; a.geomTable = c->dGeomTable; a.lum = c->dLum;
-    a.lumtot = c->dLumtot; a.cdf = c->dCdf; a.emissionBias = c->emissionBias;
-    a.ninstr = (int)c->instr.size(); a.instr = c->dInstr; a.nsed = c->nsed;
-    a.npp = npp; a.first = first; a.end = first + count; a.seed = seed;
-    a.sliceLo = sliceLo; a.sliceCnt = sliceCnt;
-    a.tag = (unsigned)phase | (cycle << 2);  // Philox counter word 1: streams differ per phase and cycle
-    a.phase = phase;
-    a.peel = phase != SKIRT_PHASE_DUST_SELFABS;
-    a.continuous = continuous ? 1 : 0;
-    a.cellLv = c->dCellLv; a.cellCdf = c->dCellCdf; a.cellGuide = c->dCellGuide; a.cellLtot = c->dCellLtot; a.cellBias = c->cellBias;
-    a.cellNode = c->dCellNode;
-    a.minWeightReduction = p->min_weight_reduction; a.minScatt = p->min_scatt_events; a.xi = p->scatt_bias;
-    // absorption: the stellar phase as its parameters say (into Labs), self-absorption always (into the
-    // dust Labs), dust emission never (MonteCarloSimulation.cpp:287, PanMonteCarloSimulation.cpp:223, 331)
-    a.store = phase == SKIRT_PHASE_STELLAR ? (p->store_absorption ? 1 : 0) : (phase == SKIRT_PHASE_DUST_SELFABS ? 1 : 0);
-    a.hasDust = p->has_dust ? 1 : 0;
-    if (a.store && !c->dLabs) return fail(c, SKIRT_ERR_STATE, "no Labs buffer");
-    // the trace kernel adds to Labs through a buffer descriptor (32-bit byte offsets, one byte past the end
-    // for the drain's empty lanes) while the table holds at most 4 GiB - 8 (e.g. 2^21 cells x 255
-    // wavelengths), with global atomics beyond (SKIRT_AMD_LABS_GLOBAL=1 forces them: tests)
-    const uint64_t labsElems = (uint64_t)c->labsStride * (uint64_t)c->nlambda;
-    // 2^32 elements or more (32 GiB): the buffered adds carry 40-bit element indices (SKIRT_AMD_LABS_HI=1 forces
-    // that path: tests); 2^40 elements at most
-    if (a.store && labsElems >= (1ull << 40)) return fail(c, SKIRT_ERR_UNSUPPORTED, "Labs table of 2^40 elements or more");
-    const bool forceHi = getenv("SKIRT_AMD_LABS_HI") && atoi(getenv("SKIRT_AMD_LABS_HI")) != 0;
-    a.labsHi = (a.store && (forceHi || labsElems > 0xffffffffull)) ? 1 : 0;
-    const bool forceGlobal = getenv("SKIRT_AMD_LABS_GLOBAL") && atoi(getenv("SKIRT_AMD_LABS_GLOBAL")) != 0;
-    a.labsGlobal = (forceGlobal || a.labsHi || labsElems * sizeof(double) > 0xfffffff8ull) ? 1 : 0;
-    a.labs = phase == SKIRT_PHASE_DUST_SELFABS ? c->dLabsDust : c->dLabs;
-    a.labsBytes = a.labsGlobal ? 0u : (unsigned)(labsElems * sizeof(double));
-    // The trace waves add into K replicas of the table (wave w into w % K), folded into it at the phase end:
-    // the adds to one cell spread over K lines, which the memory-side atomic unit works on side by side.
-    // In the stellar phase the replicas pay while they stay near the MALL (256 MB): C3 (a 129 MB table) 2:
-    // +1.1 %, 3: +1.2 %, 4: +0.8 %, 6: -1 %, 8: -3.4 %; C2 (21 MB) 4: +2 %, 8: +3.3 %. The self-absorption
-    // cycles' adds crowd onto fewer lines and gain up to 6: C5 with 3 in the stellar phase and 6 in the
-    // cycles +9.0 % against none, +3.6 % against 2 everywhere; C3 +1.2 % (profiles/r05_labs_copies_ab.txt).
-    // K = 400 MiB (self-absorption: 800 MiB) / the table, at most 8; SKIRT_AMD_LABS_COPIES sets it (1: none)
-    double* const labsTarget = a.labs;
-    a.labsCopies = 1;
-    a.labsCopyStride = 0;
-    {
-        const uint64_t tableBytes = (uint64_t)a.labsBytes > 0 ? (uint64_t)a.labsBytes : 1;
-        const uint64_t budget = phase == SKIRT_PHASE_DUST_SELFABS ? (800ull << 20) : (400ull << 20);
-        const int Kauto = (int)std::min<uint64_t>(8, std::max<uint64_t>(1, budget / tableBytes));
-        const int K = getenv("SKIRT_AMD_LABS_COPIES") ? atoi(getenv("SKIRT_AMD_LABS_COPIES")) : Kauto;
-        const uint64_t stride = ((uint64_t)a.labsBytes + 255) & ~255ull;
-        if (a.store && !a.labsGlobal && K > 1 && K <= 64 && stride * (uint64_t)K <= 0xfffffff0ull) {
-            const size_t need = (size_t)stride * K;
-            if (c->labsRepBytes < need) {
-                if (c->dLabsRep) HIPCHECK(c, hipFree(c->dLabsRep));
-                c->dLabsRep = nullptr;
-                c->labsRepBytes = 0;
-                HIPCHECK(c, hipMalloc(&c->dLabsRep, need));
-                HIPCHECK(c, hipMemsetAsync(c->dLabsRep, 0, need, c->stream));
-                c->labsRepBytes = need;
-            }
-            if (c->labsRepDirty) {  // (the failed phase's trace launches may still run on the pipeline streams)
-                HIPCHECK(c, hipDeviceSynchronize());
-                HIPCHECK(c, hipMemsetAsync(c->dLabsRep, 0, c->labsRepBytes, c->stream));
-            }
-            c->labsRepDirty = true;  // until the fold at this phase's end
-            a.labs = c->dLabsRep;
-            a.labsCopies = K;
-            a.labsCopyStride = (unsigned)stride;
-        }
-    }
-    a.tally = c->dTally;
-    a.error = c->dError; a.stats = c->dStats;
-    a.crossed = c->dCrossed; a.crossedBins = c->crossedBins;
-    a.claim = c->dClaim;
-    a.threshold = c->threshold > 0 ? c->threshold : (c->gridKind == SKIRT_GRID_VORONOI ? 8 : 16);
-    a.walkBack = c->walkBack >= 0 ? c->walkBack : (c->gridKind == SKIRT_GRID_VORONOI ? 1 : 0);
-    // LDS layout (doubles): mesh | optics | instruments | SED sums
-    int off = 0;
-    a.ldsMeshOff = off;
-    const bool meshGrid = c->gridKind == SKIRT_GRID_CARTESIAN || c->gridKind == SKIRT_GRID_CYLINDER2D ||
-                          c->gridKind == SKIRT_GRID_SPHERE1D || c->gridKind == SKIRT_GRID_SPHERE2D;
-    off += (meshGrid && a.hasDust) ? (c->nx + c->ny + c->nz + 3) : 0;
-    off += leafMap ? 3 * (c->mapN + 1) : 0;
-    off = (off + 1) & ~1;
-    a.ldsOptOff = off;
-    off += 4 * a.ncomp * a.nlambda;
-    off = (off + 1) & ~1;
-    a.ldsInstrOff = off;
-    off += a.ninstr * (int)(sizeof(DevInstr) / sizeof(double));
-    a.ldsSedOff = off;
-    off += c->nsed;
-    // a phase storing no absorption with one component runs traceKernelNoStore (no Labs buffers)
-    const bool noStore = !a.store && a.ncomp == 1 && !continuous && c->gridKind != SKIRT_GRID_VORONOI &&
-                         !getenv("SKIRT_AMD_NO_NOSTORE");
-    const size_t ldsTrace = (size_t)a.ldsInstrOff * sizeof(double)          // grid tables + optics
-                            + (size_t)kSegWords * sizeof(double)                          // + segment counts
-                            + (noStore ? 0 : (size_t)kLabsBuf * kBlock * (sizeof(double) + sizeof(unsigned)))  // + Labs buffers
-                            + (a.labsHi ? (size_t)kLabsBuf * kBlock : 0);  // + their high index bytes
-    const size_t ldsEvent = (size_t)a.ldsSedOff * sizeof(double);           // + instruments
-    // budget: what one workgroup may allocate (160 KiB on gfx950). The trace and event kernels need their
-    // tables; the detect kernel keeps as many SED copies as fit (8, 4, 2, 1), or none (SEDs to the tally)
-    const size_t budget = c->ldsMax;
-    if (ldsTrace > budget || ldsEvent > budget)
-        return fail(c, SKIRT_ERR_UNSUPPORTED, "grid and optical tables do not fit in LDS (" +
-                                                  std::to_string(std::max(ldsTrace, ldsEvent)) + " of " +
-                                                  std::to_string(budget) + " bytes)");
-    // SKIRT_AMD_DET_COPIES caps the copies (tests of the fallbacks)
-    const int capCopies = getenv("SKIRT_AMD_DET_COPIES") ? atoi(getenv("SKIRT_AMD_DET_COPIES")) : kDetectCopies;
-    a.detCopies = kDetectCopies;
-    while (a.detCopies > 0 && a.detCopies > capCopies) a.detCopies >>= 1;
-    while (a.detCopies > 0 && ldsEvent + (size_t)a.detCopies * c->nsed * sizeof(double) > budget) a.detCopies >>= 1;
-    const size_t ldsDetect = ldsEvent + (size_t)a.detCopies * c->nsed * sizeof(double);
-    c->lastDetCopies = a.detCopies;
-    // launches above 64 KiB of dynamic LDS declare it first
-    if (ldsDetect > 64 * 1024)
-        HIPCHECK(c, hipFuncSetAttribute((const void*)detectKernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)ldsDetect));
-    const int kind = c->gridKind == SKIRT_GRID_CARTESIAN ? SKIRT_GRID_CARTESIAN
-                     : c->gridKind == SKIRT_GRID_VORONOI ? SKIRT_GRID_VORONOI
-                     : c->gridKind == SKIRT_GRID_CYLINDER2D ? SKIRT_GRID_CYLINDER2D
-                     : c->gridKind == SKIRT_GRID_SPHERE1D ? SKIRT_GRID_SPHERE1D
-                     : c->gridKind == SKIRT_GRID_SPHERE2D ? SKIRT_GRID_SPHERE2D
-                     : bookkeeping ? kOctreeBookkeeping
-                     : (leafMap ? (c->binTree ? kBinTreeMap : SKIRT_GRID_OCTREE) : kOctreeNodes);
-    c->lastWalk = kind == SKIRT_GRID_CARTESIAN ? SKIRT_WALK_CARTESIAN
-                  : kind == SKIRT_GRID_OCTREE  ? SKIRT_WALK_OCTREE_MAP
-                  : kind == kBinTreeMap        ? SKIRT_WALK_KDTREE_MAP
-                  : kind == kOctreeBookkeeping ? SKIRT_WALK_OCTREE_BOOKKEEPING
-                  : kind == SKIRT_GRID_VORONOI ? SKIRT_WALK_VORONOI
-                  : kind == SKIRT_GRID_CYLINDER2D ? SKIRT_WALK_CYLINDER2D
-                  : kind == SKIRT_GRID_SPHERE1D ? SKIRT_WALK_SPHERE1D
-                  : kind == SKIRT_GRID_SPHERE2D ? SKIRT_WALK_SPHERE2D
-                                               : SKIRT_WALK_TREE_NODES;
-    const bool one = a.ncomp == 1;
-    const void* traceFn = nullptr;
-    auto pick = [&](auto fn1, auto fnN, auto fn1c, auto fnNc, const void* fnNoStore) {
-        traceFn = continuous ? (one ? (const void*)fn1c : (const void*)fnNc) : (one ? (const void*)fn1 : (const void*)fnN);
-        if (noStore) traceFn = fnNoStore;
-    };
-#define SKIRT_PICK4(G, L) pick(traceKernel<G, true, false, L>, traceKernel<G, false, false, L>, traceKernel<G, true, true, L>, \
-                              traceKernel<G, false, true, L>, (const void*)traceKernelNoStore<G>)
-#define SKIRT_PICK(G) (a.labsGlobal ? SKIRT_PICK4(G, true) : SKIRT_PICK4(G, false))
-    if (kind == SKIRT_GRID_CARTESIAN) SKIRT_PICK(SKIRT_GRID_CARTESIAN);
-    else if (kind == SKIRT_GRID_OCTREE) SKIRT_PICK(SKIRT_GRID_OCTREE);
-    else if (kind == kBinTreeMap) SKIRT_PICK(kBinTreeMap);
-    else if (kind == kOctreeBookkeeping) SKIRT_PICK(kOctreeBookkeeping);
-    else if (kind == SKIRT_GRID_CYLINDER2D) SKIRT_PICK(SKIRT_GRID_CYLINDER2D);
-    else if (kind == SKIRT_GRID_SPHERE1D) SKIRT_PICK(SKIRT_GRID_SPHERE1D);
-    else if (kind == SKIRT_GRID_SPHERE2D) SKIRT_PICK(SKIRT_GRID_SPHERE2D);
-    else if (kind == SKIRT_GRID_VORONOI) {
-        if (a.labsGlobal)
-            pick(traceKernelVor<true, false, true>, traceKernelVor<false, false, true>, traceKernelVor<true, true, true>,
-                 traceKernelVor<false, true, true>, nullptr);
-        else
-            pick(traceKernelVor<true, false>, traceKernelVor<false, false>, traceKernelVor<true, true>,
-                 traceKernelVor<false, true>, nullptr);
-    }
-    else SKIRT_PICK(kOctreeNodes);
-#undef SKIRT_PICK
-#undef SKIRT_PICK4
-    if (ldsTrace > 64 * 1024)
-        HIPCHECK(c, hipFuncSetAttribute(traceFn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsTrace));
-    int tgrid = c->traceGrid;
-    if (tgrid <= 0) {
-        int per = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, traceFn, kBlock, ldsTrace) != hipSuccess || per < 1) per = 2;
-        tgrid = std::max(1, c->nCusT) * per;
-        c->traceBlocksPerCU = per;
-    }
-    // event kernel blocks per CU: 3 (3 waves/SIMD, the registers allow it). Voronoi: C4 +0.6 % against 2
-    // (profiles/r04_event_bpc_sweep.txt); the other grids, once the block reservations no longer serialize on
-    // one counter line: C3 +0.7 %, C2 +2.3 % against 2, 4 the same as 3 (profiles/r05_event_bpc_ab.txt)
-#ifndef SKIRT_EVENT_BPC
-#define SKIRT_EVENT_BPC 3
-#endif
-    const int ebpc = SKIRT_EVENT_BPC;
-    const int egrid = std::max(1, std::min((slots + kBlock - 1) / kBlock, std::max(1, c->nCusE) * ebpc));
-    const int dgrid = std::max(1, std::max(1, c->nCusE) * 4);
-
+    PhasePlan pl;
+    if ((rc = planPhase(c, phase, cycle, npp, first, count, sliceLo, sliceCnt, seed, p, pl))) return rc;
     HIPCHECK(c, hipMemsetAsync(c->dClaim, 0, sizeof(unsigned long long), c->stream));
-    HIPCHECK(c, hipMemsetAsync(c->dCtr, 0, kMaxHalves * kCtrWords * sizeof(unsigned int), c->stream));
+    HIPCHECK(c, hipMemsetAsync(c->dCtr, 0, kCtrWords * sizeof(unsigned int), c->stream));
     HIPCHECK(c, hipEventRecord(c->ev0, c->stream));
-    if (forked) {  // the pipeline streams start after the caller's stream
-        HIPCHECK(c, hipEventRecord(c->evFork, c->stream));
-        HIPCHECK(c, hipStreamWaitEvent(sE, c->evFork, 0));
-        for (int h = 0; h < halves; h++) HIPCHECK(c, hipStreamWaitEvent(sT[h], c->evFork, 0));
-    }
-    auto launchEvent = [&](const Args& aa, hipStream_t st) {
-#define SKIRT_EVENT(G, O) hipLaunchKernelGGL((eventKernel<G, O>), dim3(egrid), dim3(kBlock), ldsEvent, st, aa)
-        if (kind == SKIRT_GRID_CARTESIAN) { if (one) SKIRT_EVENT(SKIRT_GRID_CARTESIAN, true); else SKIRT_EVENT(SKIRT_GRID_CARTESIAN, false); }
-        else if (kind == SKIRT_GRID_OCTREE) { if (one) SKIRT_EVENT(SKIRT_GRID_OCTREE, true); else SKIRT_EVENT(SKIRT_GRID_OCTREE, false); }
-        else if (kind == kBinTreeMap) { if (one) SKIRT_EVENT(kBinTreeMap, true); else SKIRT_EVENT(kBinTreeMap, false); }
-        else if (kind == kOctreeBookkeeping) { if (one) SKIRT_EVENT(kOctreeBookkeeping, true); else SKIRT_EVENT(kOctreeBookkeeping, false); }
-        else if (kind == SKIRT_GRID_CYLINDER2D) { if (one) SKIRT_EVENT(SKIRT_GRID_CYLINDER2D, true); else SKIRT_EVENT(SKIRT_GRID_CYLINDER2D, false); }
-        else if (kind == SKIRT_GRID_SPHERE1D) { if (one) SKIRT_EVENT(SKIRT_GRID_SPHERE1D, true); else SKIRT_EVENT(SKIRT_GRID_SPHERE1D, false); }
-        else if (kind == SKIRT_GRID_SPHERE2D) { if (one) SKIRT_EVENT(SKIRT_GRID_SPHERE2D, true); else SKIRT_EVENT(SKIRT_GRID_SPHERE2D, false); }
-        else if (kind == SKIRT_GRID_VORONOI) { if (one) SKIRT_EVENT(SKIRT_GRID_VORONOI, true); else SKIRT_EVENT(SKIRT_GRID_VORONOI, false); }
-        else { if (one) SKIRT_EVENT(kOctreeNodes, true); else SKIRT_EVENT(kOctreeNodes, false); }
-#undef SKIRT_EVENT
-    };
-    auto launchCont = [&](const Args& aa, hipStream_t st) {
-#define SKIRT_CONT(G, O) hipLaunchKernelGGL((contKernel<G, O>), dim3(egrid), dim3(kBlock), ldsEvent, st, aa)
-        if (kind == SKIRT_GRID_CARTESIAN) { if (one) SKIRT_CONT(SKIRT_GRID_CARTESIAN, true); else SKIRT_CONT(SKIRT_GRID_CARTESIAN, false); }
-        else if (kind == SKIRT_GRID_OCTREE) { if (one) SKIRT_CONT(SKIRT_GRID_OCTREE, true); else SKIRT_CONT(SKIRT_GRID_OCTREE, false); }
-        else if (kind == kBinTreeMap) { if (one) SKIRT_CONT(kBinTreeMap, true); else SKIRT_CONT(kBinTreeMap, false); }
-        else if (kind == kOctreeBookkeeping) { if (one) SKIRT_CONT(kOctreeBookkeeping, true); else SKIRT_CONT(kOctreeBookkeeping, false); }
-        else if (kind == SKIRT_GRID_CYLINDER2D) { if (one) SKIRT_CONT(SKIRT_GRID_CYLINDER2D, true); else SKIRT_CONT(SKIRT_GRID_CYLINDER2D, false); }
-        else if (kind == SKIRT_GRID_SPHERE1D) { if (one) SKIRT_CONT(SKIRT_GRID_SPHERE1D, true); else SKIRT_CONT(SKIRT_GRID_SPHERE1D, false); }
-        else if (kind == SKIRT_GRID_SPHERE2D) { if (one) SKIRT_CONT(SKIRT_GRID_SPHERE2D, true); else SKIRT_CONT(SKIRT_GRID_SPHERE2D, false); }
-        else if (kind == SKIRT_GRID_VORONOI) { if (one) SKIRT_CONT(SKIRT_GRID_VORONOI, true); else SKIRT_CONT(SKIRT_GRID_VORONOI, false); }
-        else { if (one) SKIRT_CONT(kOctreeNodes, true); else SKIRT_CONT(kOctreeNodes, false); }
-#undef SKIRT_CONT
-    };
-    auto launchTrace = [&](const Args& aa, hipStream_t st) {
-        // the kernel picked above (traceFn), launched through its generic entry
-        void* args[] = {const_cast<Args*>(&aa)};
-        return hipLaunchKernel(traceFn, dim3(tgrid), dim3(kBlock), args, ldsTrace, st);
-    };
-    if ((int)c->pollEv.size() < kMaxHalves * kPollRing) {
-        while ((int)c->pollEv.size() < kMaxHalves * kPollRing) {
-            hipEvent_t e;
-            HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->pollEv.push_back(e);
-        }
-    }
-    // Per half, iteration it (parity q = it & 1): the event kernel consumes active list ctr[2+q] and
-    // queues rays into ctr[q] and the next active list into ctr[2+1-q]; the trace kernel walks the
-    // ctr[q] rays and resets ctr[1-q] and ctr[2+q] for the next iteration; the detect kernel turns the
-    // finished peel-off rays into detections. After every detect kernel the half's counters are copied
-    // to pinned memory behind an event; the host reads each copy kPollRing copies later (by then long
-    // complete), so it never drains a stream. A half whose active count was 0 is finished; the few
-    // iterations launched after that point find no work and exit at once.
-    // Stream order: sE runs, per half in turn, the detect kernel of the half's last iteration and the
-    // event kernel of its next one; sT[h] runs the half's trace kernels. With two halves, one half's
-    // detect + event kernels thus run while the other half's trace kernel runs (on CUs of their own when
-    // the streams are CU-masked): sE = ev0(0) ev1(0) det0(0) ev0(1) det1(0) ev1(1) ...; sT[0] = tr0(0)
-    // tr0(1) ...; each kernel waits only for its own half's previous kernel on the other stream.
-    Args ah[kMaxHalves], prev[kMaxHalves];
-    int its[kMaxHalves] = {0}, polls[kMaxHalves] = {0};
-    int pollIt[kMaxHalves][kPollRing] = {};  // the iteration count each copy was taken at
-    bool done[kMaxHalves] = {false}, pendingDet[kMaxHalves] = {false};
-    DetRec* detBase[kMaxHalves] = {};
-    for (int h = 0; h < halves; h++) {
-        ah[h] = a;
-        carvePool(c, ah[h], h);
-        detBase[h] = ah[h].det;
-    }
-    // the detect kernel of half h's last trace launch (on sE, after that launch), then the counter copy
-    // With detAside it runs on sD after the trace launch; the next iteration of the same parity, which
-    // writes that region of detection records again, waits for it (evDet). Its record count is then
-    // zeroed for that iteration's event kernel to append to.
-    bool detUsed[2] = {false, false};
-    auto detect = [&](int h) -> int {
-        pendingDet[h] = false;
-        const Args& d = prev[h];
-        hipStream_t sd = detAside ? c->sD : sE;
-        if (detAside) {
-            HIPCHECK(c, hipEventRecord(c->evDetT, sT[h]));
-            HIPCHECK(c, hipStreamWaitEvent(sd, c->evDetT, 0));
-        } else if (sE != sT[h]) {
-            HIPCHECK(c, hipStreamWaitEvent(sE, c->evT[h], 0));
-        }
-        hipLaunchKernelGGL(detectKernel, dim3(dgrid), dim3(kBlock), ldsDetect, sd, d);
-        HIPCHECK(c, hipGetLastError());
-        HIPCHECK(c, hipMemsetAsync(CTRP(d.ctr, 5 + d.parity), 0, sizeof(unsigned int), sd));
-        if (detAside) {
-            HIPCHECK(c, hipEventRecord(c->evDet[d.parity], sd));
-            detUsed[d.parity] = true;
-        }
-        return SKIRT_OK;
-    };
-    // iterations per pipeline half before the phase is declared stuck; SKIRT_AMD_MAX_ITERATIONS lowers the cap
-    // (tests of the error exits)
-    const int maxIts = getenv("SKIRT_AMD_MAX_ITERATIONS") ? atoi(getenv("SKIRT_AMD_MAX_ITERATIONS")) : 10000000;
-    int total = 0;
-    while (true) {
-        bool all = true;
-        for (int h = 0; h < halves; h++) {
-            if (done[h]) continue;
-            all = false;
-            Args& aa = ah[h];
-            if (pendingDet[h] && (rc = detect(h))) return rc;
-            if (its[h] > 0 && its[h] % kPollEvery == 0) {
-                const int slot = polls[h] % kPollRing;
-                unsigned int* hc = c->hCtr + (h * kPollRing + slot) * kCtrWords;
-                hipEvent_t pe = c->pollEv[h * kPollRing + slot];
-                if (polls[h] >= kPollRing) {
-                    // the copy made kPollRing polls ago: is the half finished?
-                    HIPCHECK(c, hipEventSynchronize(pe));
-                    if (CTR(hc, 2 + (pollIt[h][slot] & 1)) == 0) { done[h] = true; continue; }
-                }
-                HIPCHECK(c, hipMemcpyAsync(hc, aa.ctr, 8 * kCtrStride * sizeof(unsigned int), hipMemcpyDeviceToHost, sE));
-                HIPCHECK(c, hipEventRecord(pe, sE));
-                pollIt[h][slot] = its[h];
-                polls[h]++;
-            }
-            if (its[h] > maxIts) return fail(c, SKIRT_ERR_STATE, "photon phase did not terminate");
-            aa.parity = its[h] & 1;
-            aa.init = (its[h] == 0) ? 1 : 0;
-            if (detAside) {
-                // this iteration's detection records: the region of its parity, free once the detect kernel of
-                // the last iteration of that parity is done
-                aa.det = detBase[h] + (size_t)aa.parity * (size_t)(c->rayCap - c->nslots);
-                if (detUsed[aa.parity]) HIPCHECK(c, hipStreamWaitEvent(sE, c->evDet[aa.parity], 0));
-            }
-            if (aa.continuous && !aa.init) {  // the continuous peel-offs of the FILL rays that just returned
-                launchCont(aa, sE);
-                HIPCHECK(c, hipGetLastError());
-            }
-            launchEvent(aa, sE);
-            HIPCHECK(c, hipGetLastError());
-            if (!a.hasDust) { done[h] = true; its[h]++; continue; }  // every packet completes in the event kernel
-            if (sE != sT[h]) {
-                HIPCHECK(c, hipEventRecord(c->evE[h], sE));
-                HIPCHECK(c, hipStreamWaitEvent(sT[h], c->evE[h], 0));
-            }
-            if ((int)c->traceEv.size() < 2 * (c->traceLaunches + 1)) {
-                hipEvent_t e0, e1;
-                HIPCHECK(c, hipEventCreate(&e0));
-                HIPCHECK(c, hipEventCreate(&e1));
-                c->traceEv.push_back(e0);
-                c->traceEv.push_back(e1);
-            }
-            // the detect kernel of the last iteration runs beside this iteration's event kernel only
-            if (detAside && detUsed[1 - aa.parity])
-                HIPCHECK(c, hipStreamWaitEvent(sT[h], c->evDet[1 - aa.parity], 0));
-            HIPCHECK(c, hipEventRecord(c->traceEv[2 * c->traceLaunches], sT[h]));
-            HIPCHECK(c, launchTrace(aa, sT[h]));
-            HIPCHECK(c, hipGetLastError());
-            HIPCHECK(c, hipEventRecord(c->traceEv[2 * c->traceLaunches + 1], sT[h]));
-            c->traceLaunches++;
-            if (sE != sT[h]) HIPCHECK(c, hipEventRecord(c->evT[h], sT[h]));
-            if (a.ninstr > 0) { prev[h] = aa; pendingDet[h] = true; }
-            its[h]++;
-            total++;
-        }
-        if (all) break;
-    }
-    for (int h = 0; h < halves; h++)
-        if (pendingDet[h] && (rc = detect(h))) return rc;
-    int it = total;
-    c->lastIterations = it;
-    if (detAside && (detUsed[0] || detUsed[1])) {  // the caller's stream continues after the last detect kernel
-        HIPCHECK(c, hipEventRecord(c->evDetJoin, c->sD));
-        HIPCHECK(c, hipStreamWaitEvent(c->stream, c->evDetJoin, 0));
-    }
-    if (forked) {  // the caller's stream continues after the pipeline streams
-        HIPCHECK(c, hipEventRecord(c->evJoin[0], sE));
-        HIPCHECK(c, hipStreamWaitEvent(c->stream, c->evJoin[0], 0));
-        for (int h = 0; h < halves; h++) {
-            HIPCHECK(c, hipEventRecord(c->evJoin[1 + h], sT[h]));
-            HIPCHECK(c, hipStreamWaitEvent(c->stream, c->evJoin[1 + h], 0));
-        }
-    }
-    if (a.labsCopies > 1) {
-        hipLaunchKernelGGL(labsFoldKernel, dim3(2048), dim3(kBlock), 0, c->stream, labsTarget, c->dLabsRep,
-                           (size_t)labsElems, a.labsCopies, (size_t)a.labsCopyStride / sizeof(double));
+    if ((rc = runIterations(c, pl))) return rc;
+    if (pl.a.labsCopies > 1) {
+        hipLaunchKernelGGL(labsFoldKernel, dim3(2048), dim3(kBlock), 0, c->stream, pl.labsTarget, c->dLabsRep,
+                           (size_t)pl.labsElems, pl.a.labsCopies, (size_t)pl.a.labsCopyStride / sizeof(double));
         HIPCHECK(c, hipGetLastError());
         c->labsRepDirty = false;  // the fold zeroes the replicas
     }
@@ -5080,24 +5060,13 @@ int skirt_mcrt_column_densities(SkirtMcrt* c, const double* rays, int n, double*
     // the walks of the photon paths, through the node arrays for trees (equal to the leaf-map walk,
     // tests/test_gpu_parity.py::test_leaf_map_walk_equals_node_walk)
     if (e == hipSuccess) {
-        if (c->gridKind == SKIRT_GRID_CARTESIAN)
-            hipLaunchKernelGGL(columnKernel<SKIRT_GRID_CARTESIAN>, grid, dim3(kBlock),
-                               (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
-        else if (c->gridKind == SKIRT_GRID_CYLINDER2D)
-            hipLaunchKernelGGL(columnKernel<SKIRT_GRID_CYLINDER2D>, grid, dim3(kBlock),
-                               (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
-        else if (c->gridKind == SKIRT_GRID_SPHERE1D)
-            hipLaunchKernelGGL(columnKernel<SKIRT_GRID_SPHERE1D>, grid, dim3(kBlock),
-                               (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
-        else if (c->gridKind == SKIRT_GRID_SPHERE2D)
-            hipLaunchKernelGGL(columnKernel<SKIRT_GRID_SPHERE2D>, grid, dim3(kBlock),
-                               (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double), c->stream, a, d, n, d + 6 * (size_t)n);
-        else if (c->gridKind == SKIRT_GRID_VORONOI)
-            hipLaunchKernelGGL(columnKernel<SKIRT_GRID_VORONOI>, grid, dim3(kBlock), 0, c->stream, a, d, n, d + 6 * (size_t)n);
-        else if (c->search == SKIRT_TREE_BOOKKEEPING)
-            hipLaunchKernelGGL(columnKernel<kOctreeBookkeeping>, grid, dim3(kBlock), 0, c->stream, a, d, n, d + 6 * (size_t)n);
-        else
-            hipLaunchKernelGGL(columnKernel<kOctreeNodes>, grid, dim3(kBlock), 0, c->stream, a, d, n, d + 6 * (size_t)n);
+        const int kind = walkKind(c, true);
+        const size_t lds = walkOf(kind).meshInLds ? (size_t)(c->nx + c->ny + c->nz + 3) * sizeof(double) : 0;
+        withWalk(kind, [&](auto g) {
+            constexpr int G = decltype(g)::value;
+            constexpr int W = (G == SKIRT_GRID_OCTREE || G == kBinTreeMap) ? kOctreeNodes : G;  // no leaf maps here
+            hipLaunchKernelGGL(columnKernel<W>, grid, dim3(kBlock), lds, c->stream, a, d, n, d + 6 * (size_t)n);
+        });
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + 6 * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -5158,15 +5127,6 @@ void skirt_mcrt_destroy(SkirtMcrt* c) {
     if (c->dLabsRep) (void)hipFree(c->dLabsRep);
     for (hipEvent_t e : c->traceEv) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->pollEv) (void)hipEventDestroy(e);
-    if (c->evFork) (void)hipEventDestroy(c->evFork);
-    for (hipEvent_t e : c->evJoin)
-        if (e) (void)hipEventDestroy(e);
-    for (int h = 0; h < kMaxHalves; h++) {
-        if (c->evE[h]) (void)hipEventDestroy(c->evE[h]);
-        if (c->evT[h]) (void)hipEventDestroy(c->evT[h]);
-        if (c->sT[h]) (void)hipStreamDestroy(c->sT[h]);
-    }
-    if (c->sE) (void)hipStreamDestroy(c->sE);
     if (c->sD) (void)hipStreamDestroy(c->sD);
     for (hipEvent_t e : {c->evDetT, c->evDet[0], c->evDet[1], c->evDetJoin})
         if (e) (void)hipEventDestroy(e);

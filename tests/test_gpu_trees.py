@@ -65,3 +65,26 @@ def test_kd_tree_leaf_map_walk_equals_node_walk(tmp_path, name, monkeypatch):
     np.testing.assert_allclose(da, db, rtol=1e-10, atol=1e-300)
     np.testing.assert_allclose(fa, fb, rtol=1e-10, atol=1e-300)
 
+
+@pytest.mark.parametrize("a,b,rtol", [("oct_pan_td", "oct_pan_bk", 1e-9), ("bin_pan", "bin_pan_td", 1e-12)])
+def test_column_densities_do_not_depend_on_the_search_method(tmp_path, a, b, rtol):
+    """The column kernel walks trees through the node arrays, with the neighbour lists or (Bookkeeping) the
+    breadth-first numbering. The two models of a pair differ only in searchMethod: the same tree and the same
+    densities, so both walks cross the same leaf boxes in the same order and add the same rho * ds products:
+    1e-12. The Bookkeeping walk places its steps with its own arithmetic and differs from the neighbour walk
+    by 1.43e-10 relative at most on these rays: ten times that, capped at the suite's same-stream tolerance
+    of 1e-9."""
+    pc = 3.0856775814913673e16  # m
+    rng = np.random.default_rng(7)
+    origins = rng.uniform(-400.0, 400.0, (16, 3)) * pc  # the grid is the +-500 pc cube
+    k = rng.normal(size=(16, 3))  # no ray runs along a cell face
+    k /= np.linalg.norm(k, axis=1)[:, None]
+    rays = np.hstack([origins, k])
+    cols = []
+    for name in (a, b):
+        sim = S.Simulation(T.write(name, str(tmp_path)), packages=10)
+        sim.attach(0)
+        cols.append(sim.column_densities(rays))
+    assert np.all(cols[0] > 0) and np.all(cols[1] > 0)
+    np.testing.assert_allclose(cols[0], cols[1], rtol=rtol, atol=0)
+
