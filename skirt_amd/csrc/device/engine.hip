@@ -114,11 +114,11 @@ enum PeelCat : unsigned { CAT_STAR_DIRECT = 0, CAT_STAR_SCATTERED = 1, CAT_DUST_
 struct __attribute__((aligned(16))) RayRec {
     double x, y, z;        // c0-c1: start point
     double dx, dy, dz;     // c1-c2: direction
-    double s0;             // c3: path length before the grid (Voronoi) or 0
+    double s0;             // c3: path length before the grid (Voronoi) | a fused FILL ray's termination threshold | 0
     double param;          // c3: FILL: packet luminosity L; WALK: optical depth to reach; PEEL: peel-off L
     int idx;               // c4: FILL/WALK: slot; PEEL: detection record
     unsigned flags;        // c4: mode | cat << 2 | instrument << 4 | scattering level << 10 | ell << 18
-    int ci, cj;            // c4: Voronoi: first cell and where its block starts
+    int ci, cj;            // c4: Voronoi: first cell and where its block starts | a fused FILL ray's deviate (Args::fuseU)
 };
 static_assert(sizeof(RayRec) == 80, "ray record layout");
 
@@ -166,6 +166,59 @@ __device__ __forceinline__ unsigned rayCat(unsigned f) { return (f >> 2) & 3u; }
 __device__ __forceinline__ int rayInstr(unsigned f) { return (int)((f >> 4) & 63u); }
 __device__ __forceinline__ int rayLevel(unsigned f) { return (int)((f >> 10) & 255u); }
 __device__ __forceinline__ int rayEll(unsigned f) { return (int)(f >> 18); }
+
+// What follows a finished FILL ray: the end of fillOpticalDepth + simulateescapeandabsorption, the
+// termination test and the optical depth of the interaction (Random::exponcutoff and the composite biasing
+// with weight p/q, MonteCarloSimulation.cpp:519-534). One function for the event kernel, which draws from
+// the packet's stream, and for the trace lane of a fused FILL ray, which holds the two deviates the event
+// kernel drew ahead from a copy of that stream (FillDrawsAhead): both decide with the same operations on
+// the same bits. FILL_FALLBACK: more than those deviates are needed (exponcutoff's rejection loop fired) or
+// taupath is negative, NaN or infinite -- the event kernel finishes either, the lane only reports it.
+enum FillStatus : int { FILL_TERMINATED = 0, FILL_NO_WALK = 1, FILL_WALK = 2, FILL_FALLBACK = 3 };
+// the composite biasing's weight p/q applied to L (MonteCarloSimulation.cpp:529-533)
+__device__ __forceinline__ double fillBiasWeight(double L, double tauint, double taupath, double xi) {
+    const double pr = -exp(-tauint) / expm1(-taupath);
+    const double q = (1.0 - xi) * pr + xi / taupath;
+    return L * (pr / q);
+}
+// Lsca: the scattered luminosity of a multi-component path; albedo: of the one component (ONECOMP);
+// thr: Lth once the packet has its minimum of scatterings, else 0; draws: biased(xi) (X < xi, asked only
+// when xi != 0), then uniform(), in the stream's order. L is updated (the weight too, unless FILL_FALLBACK).
+template <bool ONECOMP, class Draws>
+__device__ __forceinline__ int decideFill(double taupath, double& L, double Lsca, double albedo, double thr, double xi,
+                                          Draws& draws, double& tauint) {
+    tauint = 0.0;  // taupath == 0: no propagation (MonteCarloSimulation.cpp:522)
+    if (taupath < 0.0 || isnan(taupath) || isinf(taupath)) return FILL_FALLBACK;
+    if (ONECOMP) L = L * albedo * (-expm1(-taupath));
+    else L = Lsca;
+    if (L <= 0 || L <= thr) return FILL_TERMINATED;
+    if (taupath == 0.0) return FILL_NO_WALK;
+    const bool biased = xi != 0.0 && draws.biased(xi);
+    const double u = draws.uniform();
+    double t;
+    if (biased || taupath < 1e-10) t = u * taupath;
+    else {
+        const double norm = 1.0 - exp(-taupath);
+        t = -log(1.0 - u * norm);
+        if (t > taupath) return FILL_FALLBACK;  // exponcutoff draws again
+    }
+    if (xi != 0.0) L = fillBiasWeight(L, t, taupath, xi);
+    tauint = t;
+    return t > 0 ? FILL_WALK : FILL_NO_WALK;  // tauint == 0: the interaction point is where the packet is
+}
+// the deviates of decideFill from the packet's stream
+struct FillDrawsStream {
+    PacketRng& rng;
+    __device__ __forceinline__ bool biased(double xi) { return rng.uniform() < xi; }
+    __device__ __forceinline__ double uniform() { return rng.uniform(); }
+};
+// and as the event kernel drew them ahead for the trace lane
+struct FillDrawsAhead {
+    bool b;
+    double u;
+    __device__ __forceinline__ bool biased(double) const { return b; }
+    __device__ __forceinline__ double uniform() const { return u; }
+};
 
 struct LeafEntry;
 
@@ -345,6 +398,15 @@ struct Args {
     int* svcell;                 // Voronoi: the cell of the packet's position (cellIndex), kNoCell if not known
     uint32_t *splo, *sphi, *sblock, *sw2, *sw3, *shave;
     double *resA, *resB;         // per slot: FILL -> tau, Lsca | WALK -> distance
+    // fuse != 0: every FILL ray is fused -- its lane decides the interaction depth itself (decideFill) and walks
+    // on to it along its own record. Per slot: WALK -> distance, now in resS (resA keeps tau for the event
+    // kernel's own draws) | a FILL ray whose lane did not walk -> -1
+    double* resS;
+    // the lane's deviate u (negative: X < xi was drawn before it) and termination threshold: they travel in the
+    // record's ci, cj and s0, which only rays entered by the event kernel (Voronoi) use; those rays find them
+    // here, per slot
+    double *fuseU, *fuseThr;
+    int fuse;                    // 0: FILL and WALK rays queued apart | 1: fused | 2: fused, odd slots fall back (tests)
     RayRec* rays;
     DetRec* det;                 // detection records of the peel-off rays
     int* act[2];                 // active slot lists (double buffered)
@@ -1627,6 +1689,19 @@ struct Tracer {
     unsigned labsOob = 0;             // a byte offset past every replica: the empty lanes' adds are dropped
     int npend = 0;
     unsigned gstep = 0;  // grid steps of the wave (drainStep's round robin)
+    // a fused FILL ray (Args::fuse): the deviate and the termination threshold its lane decides with when the
+    // ray ends (decideFill). On a walk the lane is marked for re-entry (kLaneWalkOn in the idle lane's queue
+    // index, else 0) and the deviate's place holds the optical depth to reach. They live in registers a FILL ray
+    // leaves unused where there are any: with one component it sums no scattered luminosity (f2), and in a
+    // kernel without Labs adds it carries no exp(-tau) (f1)
+    double fu = 0, fthr = 0;
+    static constexpr unsigned kLaneWalkOn = 1u << 31;  // (the queue holds fewer than 2^31 records)
+    // Not with continuous scattering (Args::fuse is 0 there), and not in the node-array walk's no-store kernel:
+    // at 4 waves per SIMD it has 3 registers to spare, and the decision's exp and log would spill
+    // (planPhase leaves those phases unfused)
+    static constexpr bool kFuse = !CONT && (STORE || GRID != kOctreeNodes);
+    __device__ __forceinline__ double& fillThr(Ray& r) { return ONECOMP ? r.f2 : fthr; }
+    __device__ __forceinline__ double& fillU(Ray& r) { return (ONECOMP && !STORE) ? r.f1 : fu; }
 
     __device__ __forceinline__ void drain() {
         static_assert(kLabsBuf >= 2 && kLabsBuf <= 64 && (kLabsBuf & (kLabsBuf - 1)) == 0, "kLabsBuf: power of 2");
@@ -1767,8 +1842,9 @@ struct Tracer {
     }
 
     // load queued ray `id` and enter the grid: the part of the path before the grid (segments outside
-    // it, m = -1) and the first cell (DustGrid::path); an empty path finishes the ray at once
-    __device__ __forceinline__ void load(Ray& r, unsigned id) {
+    // it, m = -1) and the first cell (DustGrid::path); an empty path finishes the ray at once.
+    // walkOn: the lane's own fused FILL record again, now as the WALK ray to the optical depth in fillU
+    __device__ __forceinline__ void load(Ray& r, unsigned id, bool walkOn) {
         const double2* c = reinterpret_cast<const double2*>(a.rays + id);
         const double2 c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
         const int4 c6 = reinterpret_cast<const int4*>(c)[4];
@@ -1782,6 +1858,10 @@ struct Tracer {
         r.param = c3.y;
         r.idx = c6.x;
         r.flags = (unsigned)c6.y;
+        if (kFuse && walkOn) {
+            r.param = fillU(r);
+            r.flags = (r.flags & ~3u) | RAY_WALK;
+        }
         r.mode = rayMode(r.flags);
         r.ell = rayEll(r.flags);
         r.tau = 0;
@@ -1790,11 +1870,17 @@ struct Tracer {
         if (r.mode == RAY_FILL)
             printf("E L %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", r.ell, r.x, r.y, r.z, r.dx, r.dy, r.dz, r.param);
 #endif
-        r.s = c3.x;
+        // the path before the grid of a ray the event kernel entered; the other records' s0, ci, cj are free
+        // for a fused FILL ray's threshold and deviate
+        r.s = kEnterInEvent<GRID> ? c3.x : 0.0;
         r.kext = sh.kext[r.ell];
         // FILL: f1 = exp(-tau) = 1, f2 = scattered luminosity; WALK: tau and s at the last segment end
         r.f1 = (r.mode == RAY_FILL) ? 1.0 : 0.0;
-        r.f2 = (r.mode == RAY_WALK) ? c3.x : 0.0;
+        r.f2 = (r.mode == RAY_WALK) ? r.s : 0.0;
+        if (kFuse && a.fuse && r.mode == RAY_FILL) {
+            fillU(r) = kEnterInEvent<GRID> ? a.fuseU[r.idx] : __hiloint2double(c6.w, c6.z);
+            fillThr(r) = kEnterInEvent<GRID> ? a.fuseThr[r.idx] : c3.x;
+        }
         // the segments before the grid of a ray the event kernel entered travel in the first cell's top bits
         // (a ray the event kernel entered brings its segments before the grid in the first cell's top bits)
         nseg = kEnterInEvent<GRID> ? ((unsigned)c6.z >> kOutsideShift) : 0u;
@@ -1809,15 +1895,33 @@ struct Tracer {
         }
     }
 
-    // the ray ended (grid edge or WALK target reached): deliver its result
-    __device__ __forceinline__ void finish(const Ray& r) {
+    // the ray ended (grid edge or WALK target reached): deliver its result. The lane of a fused FILL ray
+    // decides what the event kernel will decide (decideFill) and, where the packet walks, takes the WALK
+    // upon itself (kLaneWalkOn: the pull block loads the lane's record again, Tracer::load)
+    __device__ __forceinline__ void finish(Ray& r) {
         atomicAdd(&waveSegs[(threadIdx.x >> 6) * 3 + (r.mode == RAY_FILL ? 0 : r.mode == RAY_WALK ? 1 : 2)], nseg);
         if (a.crossed && r.mode != RAY_WALK) crossedAdd(a, nseg);
+        unsigned walkOn = 0;
+        double* const walked = (kFuse && a.fuse) ? a.resS : a.resA;
         if (r.mode == RAY_PEEL) {
             a.det[r.idx].tau = r.tau;  // detectKernel turns it into a detection
         } else if (r.mode == RAY_FILL) {
             a.resA[r.idx] = r.tau;
             if (!ONECOMP) a.resB[r.idx] = r.f2;
+            if (kFuse && a.fuse) {
+                const double u = fillU(r);
+                FillDrawsAhead draws{u < 0.0, fabs(u)};
+                double L = r.param, tauint;
+                int st = decideFill<ONECOMP>(r.tau, L, r.f2, ONECOMP ? sh.alb[r.ell] : 0.0,
+                                              ONECOMP ? r.f2 : fthr, a.xi, draws, tauint);
+                if (a.fuse == 2 && (r.idx & 1)) st = FILL_FALLBACK;
+                if (st == FILL_WALK) {
+                    fillU(r) = tauint;
+                    walkOn = kLaneWalkOn | r.id;
+                } else {
+                    a.resS[r.idx] = -1.0;
+                }
+            }
         } else {
             // DustGridPath::pathlength: interpolate inside the crossing segment; if the path ended first
             // (target >= tau of the path), the end of the last segment
@@ -1827,8 +1931,9 @@ struct Tracer {
                 if (r.tau > tauint) s = r.f2 + ((tauint - r.f1) / (r.tau - r.f1)) * (r.s - r.f2);
                 else s = r.f2;
             }
-            a.resA[r.idx] = s;
+            walked[r.idx] = s;
         }
+        r.id = walkOn;  // (the ray is over: its lane is idle)
     }
 };
 
@@ -2190,6 +2295,7 @@ __device__ __forceinline__ void traceBody(const Args& a) {
     const unsigned int nrays = nfront + CTR(a.ctr, 8 + a.parity);
     Ray r;
     r.mode = RAY_NONE;
+    r.id = 0;
     bool done = false;
     // the wave reserves queue ids kPullChunk at a time and hands them to its idle lanes; the next
     // reservation is requested while the current one still lasts, so a pull rarely waits for the atomic
@@ -2209,8 +2315,11 @@ __device__ __forceinline__ void traceBody(const Args& a) {
         const unsigned long long amask = __ballot(r.mode != RAY_NONE);
         if (imask == 0 && amask == 0) break;
         if (imask != 0 && (amask == 0 || __popcll(imask) >= a.threshold)) {
-            const unsigned int rank = (unsigned int)__popcll(imask & ((1ull << lane) - 1ull));
-            const unsigned int k = (unsigned int)__popcll(imask);
+            // a lane marked for re-entry takes no queue id: it loads its own record again, as the WALK ray
+            const bool walkOn = idle && (r.id & T.kLaneWalkOn) != 0;
+            const unsigned long long pmask = imask & ~__ballot(walkOn);
+            const unsigned int rank = (unsigned int)__popcll(pmask & ((1ull << lane) - 1ull));
+            const unsigned int k = (unsigned int)__popcll(pmask);
             const unsigned int avail = curEnd - cur;
             if (avail < k && !haveNext) { nxt = reserve(); haveNext = true; }
             const unsigned int id = rank < avail ? cur + rank : nxt + (rank - avail);
@@ -2218,8 +2327,8 @@ __device__ __forceinline__ void traceBody(const Args& a) {
             else { cur = nxt + (k - avail); curEnd = nxt + kPullChunk; haveNext = false; }
             if (!haveNext && curEnd - cur < kPullChunk / 2 && cur < nrays) { nxt = reserve(); haveNext = true; }
             if (idle) {
-                if (id >= nrays) done = true;
-                else T.load(r, id < nfront ? id : (unsigned)a.rayCap - 1u - (id - nfront));  // a RAY_NONE record (empty path) leaves the lane idle
+                if (!walkOn && id >= nrays) done = true;
+                else T.load(r, walkOn ? r.id & ~T.kLaneWalkOn : id < nfront ? id : (unsigned)a.rayCap - 1u - (id - nfront), walkOn);  // a RAY_NONE record (empty path) leaves the lane idle
             }
             // vmcnt(0) here, on the pull's path: without it the waitcnt pass put one at the join with the steps,
             // where a while-iteration without a pull then also waited for the last step's Labs atomic (C2 +1-2 %,
@@ -2348,7 +2457,8 @@ struct Events {
     // queues ray `pos`. The trace kernel enters the grid, except for Voronoi grids (kEnterInEvent): their
     // cellIndex loops over a block's site list, which costs the trace kernel more than it costs here. A
     // path found empty here (no dust system, or a Voronoi ray missing the grid) is finished here.
-    __device__ __forceinline__ void emitRay(unsigned pos, const Packet& p, double dx, double dy, double dz, double prm,
+    // Returns whether a ray was queued.
+    __device__ __forceinline__ bool emitRay(unsigned pos, const Packet& p, double dx, double dy, double dz, double prm,
                                             int idx, unsigned flags, int& vcell) {
         Ray r;
         r.x = p.rx; r.y = p.ry; r.z = p.rz;
@@ -2375,11 +2485,12 @@ struct Events {
         if (!entered) {
             if (mode != RAY_PEEL) {  // a peel-off's detection record already holds tau = 0
                 a.resA[idx] = 0.0;  // FILL: tau = 0 (and no scattered luminosity); WALK: s = 0
+                if (mode == RAY_WALK && a.fuse) a.resS[idx] = 0.0;
                 if (!ONECOMP) a.resB[idx] = 0.0;
                 if (mode == RAY_FILL && a.continuous) a.pathCnt[idx] = 0;  // an empty path: no dust segments
             }
             dst[4] = make_int4(idx, (int)RAY_NONE, 0, 0);
-            return;
+            return false;
         }
         double2* d2 = reinterpret_cast<double2*>(dst);
         d2[0] = make_double2(r.x, r.y);
@@ -2388,6 +2499,7 @@ struct Events {
         d2[3] = make_double2(r.s, prm);
         // (the segments before the grid, for the cells-crossed histogram, in the first cell's top bits)
         dst[4] = make_int4(idx, (int)flags, r.ci | (int)(min(nseg, 7u) << kOutsideShift), r.cj);
+        return true;
     }
 
     __device__ __forceinline__ void load(int s, Packet& p) const {
@@ -2767,29 +2879,17 @@ struct Events {
         return true;
     }
 
-    // simulatepropagation part 1: the optical depth of the interaction (Random::exponcutoff and the
-    // composite biasing with weight p/q, MonteCarloSimulation.cpp:519-534)
-    __device__ __forceinline__ double sampleTau(Packet& p, double taupath) const {
-        double tauint = -1.0;
-        if (a.xi != 0.0) {
-            const double X = p.rng.uniform();
-            if (X < a.xi) tauint = p.rng.uniform() * taupath;
-        }
-        if (tauint < 0.0) {
-            if (taupath < 1e-10) tauint = p.rng.uniform() * taupath;
-            else {
-                const double norm = 1.0 - exp(-taupath);
-                double x = -log(1.0 - p.rng.uniform() * norm);
-                while (x > taupath) x = -log(1.0 - p.rng.uniform() * norm);
-                tauint = x;
-            }
-        }
-        if (a.xi != 0.0) {
-            const double pr = -exp(-tauint) / expm1(-taupath);
-            const double q = (1.0 - a.xi) * pr + a.xi / taupath;
-            p.L = p.L * (pr / q);
-        }
-        return tauint;
+    // decideFill's termination threshold: Lth once the packet has scattered minScatt times
+    __device__ __forceinline__ double fillThreshold(const Packet& p) const { return p.nscatt >= a.minScatt ? p.Lth : 0.0; }
+
+    // simulatepropagation part 1 where decideFill left off (FILL_FALLBACK): Random::exponcutoff draws until
+    // a deviate falls inside the path, then the composite biasing's weight
+    __device__ __forceinline__ double exponCutoffAgain(Packet& p, double taupath) const {
+        const double norm = 1.0 - exp(-taupath);
+        double x = -log(1.0 - p.rng.uniform() * norm);
+        while (x > taupath) x = -log(1.0 - p.rng.uniform() * norm);
+        if (a.xi != 0.0) p.L = fillBiasWeight(p.L, x, taupath, a.xi);
+        return x;
     }
 };
 
@@ -2943,12 +3043,16 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
         if (round + 1 < rounds) slotNext = (wn < nwork) ? (a.init ? (int)wn : actIn[wn]) : 0;
         Packet p;
         p.state = S_NEW;
-        double resA = 0.0, resB = 0.0;
+        double resA = 0.0, resB = 0.0, resS = -1.0;
         int vcell = kNoCell;  // Voronoi: the cell of the packet's position, while it stays there
         if (valid && !a.init) {
             E.load(slot, p);
             resA = a.resA[slot];
             if (!ONECOMP) resB = a.resB[slot];
+            if (a.fuse) {
+                resS = a.resS[slot];
+                if (p.state == S_WALK) resA = resS;  // (a queued WALK ray's distance)
+            }
             if (kEnterInEvent<GRID>) vcell = a.svcell[slot];
         }
         int peel = PEEL_NONE;
@@ -2959,21 +3063,28 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
             if (p.state == S_FILL) {
                 // end of fillOpticalDepth + simulateescapeandabsorption; termination; simulatepropagation
                 const double taupath = resA;
-                if (taupath < 0.0 || isnan(taupath) || isinf(taupath)) {
-                    atomicOr(a.error, ERR_TAU);
+                FillDrawsStream draws{p.rng};
+                double tauint;
+                int st = decideFill<ONECOMP>(taupath, p.L, resB, ONECOMP ? sh.alb[p.ell] : 0.0, E.fillThreshold(p), a.xi,
+                                             draws, tauint);
+                if (st == FILL_FALLBACK) {
+                    if (taupath < 0.0 || isnan(taupath) || isinf(taupath)) {
+                        atomicOr(a.error, ERR_TAU);
+                        st = FILL_TERMINATED;
+                    } else {
+                        tauint = E.exponCutoffAgain(p, taupath);
+                        st = tauint > 0 ? FILL_WALK : FILL_NO_WALK;
+                    }
+                    resS = -1.0;  // (what the lane of a fused ray left there)
+                }
+                if (st == FILL_TERMINATED) {
                     p.state = S_NEW;
                 } else {
-                    if (ONECOMP) p.L = p.L * sh.alb[p.ell] * (-expm1(-taupath));
-                    else p.L = resB;
-                    if (p.L <= 0 || (p.L <= p.Lth && p.nscatt >= a.minScatt)) {
-                        p.state = S_NEW;
-                    } else {
-                        p.state = S_WALK;
-                        double tauint = 0.0;  // taupath == 0: no propagation (MonteCarloSimulation.cpp:522)
-                        if (taupath != 0.0) tauint = E.sampleTau(p, taupath);
-                        if (tauint > 0) { mainMode = RAY_WALK; mainParam = tauint; }
-                        else resA = 0.0;  // no walk: the interaction point is where the packet is
-                    }
+                    p.state = S_WALK;
+                    // a fused ray's lane walked on to the interaction point, unless it fell back
+                    if (st == FILL_WALK && resS >= 0.0) resA = resS;
+                    else if (st == FILL_WALK) { mainMode = RAY_WALK; mainParam = tauint; }
+                    else resA = 0.0;  // no walk: the interaction point is where the packet is
                 }
             }
             if (p.state == S_WALK && mainMode == RAY_NONE) {
@@ -3061,6 +3172,7 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
             nray = 0;
         }
         int inext = 0;  // next instrument to consider for a peel-off
+        int fillAt = -1;  // where the lane's FILL ray was queued, if it enters the grid
         for (int k = 0; k < nray; k++) {
             double dx, dy, dz, prm;
             int idx;
@@ -3101,12 +3213,33 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
                 flags = mainMode | ((unsigned)p.ell << 18);
                 at = back ? (unsigned)a.rayCap - 1u - wpos : pos++;
             }
-            E.emitRay(at, p, dx, dy, dz, prm, idx, flags, vcell);  // (one call site: one inlined grid entry)
+            const bool in = E.emitRay(at, p, dx, dy, dz, prm, idx, flags, vcell);  // (one call site: one inlined grid entry)
+            if (k >= npeel && in && mainMode == RAY_FILL) fillAt = (int)at;
         }
         // the slot stays active while it has a FILL/WALK ray in flight
         if (active) actOut[apos] = slot;
         if (valid) E.store(slot, p);
         if (kEnterInEvent<GRID> && valid) a.svcell[slot] = vcell;
+        // A fused FILL ray: its lane gets the deviates that this packet's next visit will draw (from a copy
+        // of the counter-based stream: the packet's own does not advance; X < xi as the sign of u) and that
+        // visit's termination threshold (decideFill). Added to the queued record here, where the round
+        // holds little else in registers: in its s0, ci and cj, which only a ray entered by the event
+        // kernel uses (those find them per slot)
+        if (a.fuse && fillAt >= 0) {
+            PacketRng ahead = p.rng;
+            const bool biased = a.xi != 0.0 && ahead.uniform() < a.xi;
+            const double u = ahead.uniform();
+            const double fu = biased ? -u : u, fthr = E.fillThreshold(p);
+            RayRec* rec = a.rays + fillAt;
+            if (kEnterInEvent<GRID>) {
+                a.fuseU[slot] = fu;
+                a.fuseThr[slot] = fthr;
+            } else {
+                rec->s0 = fthr;
+                rec->ci = __double2loint(fu);
+                rec->cj = __double2hiint(fu);
+            }
+        }
     }
     const unsigned long long vals[8] = {E.packets, E.segFill, E.segWalk, E.segPeel, E.detects, 0, 0, 0};
     flushStats(a, vals);
@@ -3326,6 +3459,14 @@ struct SkirtMcrt {
     // runs without the atomic-free WALK paths between the absorbing FILL paths: C3 2.16e8 -> 2.08e8, C2
     // 2.9e8 -> 2.8e8; C4 9.30e7 -> 9.38e7 (profiles/r03_walk_back_ab.txt)
     int walkBack = getenv("SKIRT_AMD_WALK_BACK") ? atoi(getenv("SKIRT_AMD_WALK_BACK")) : -1;
+    // The lane of a finished FILL ray walks on to the interaction point (Args::fuse): SKIRT_AMD_FUSE_WALK=1 / 0,
+    // 2: fused with every odd slot falling back to a queued WALK ray (tests); default (-1): fused, but for
+    // Voronoi grids. Never with continuous scattering, whose peel-off kernel draws between the FILL and the walk.
+    // A scattering order then costs a packet one pipeline iteration instead of two: C3 38 -> 22 launches per
+    // step, +3.5 %; C2 +6.6 %; C5 +3.1 %. C4 -0.6 % (lane use 0.920 -> 0.918: its WALK rays, pulled last
+    // (walkBack), filled the launch tails that a lane's FILL + WALK lengthens), so Voronoi grids stay unfused
+    // (medians of three alternating runs, profiles/fused_walk_ab.txt)
+    int fuseWalk = getenv("SKIRT_AMD_FUSE_WALK") ? atoi(getenv("SKIRT_AMD_FUSE_WALK")) : -1;
     int traceBlocksPerCU = 0;  // the occupancy the last trace launch was sized for
     int lastDetCopies = 0;  // SED copies of the last run's detect kernel
     double lastMs = 0;
@@ -3451,7 +3592,7 @@ int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair) {
     const int rayCap = (int)rays;
     const size_t path = continuous ? (size_t)nslots * (kPathCap * sizeof(PathRec) + sizeof(int)) : 0;
     const size_t bytes = (size_t)rayCap * sizeof(RayRec) + (detPair ? 2 : 1) * (size_t)(rayCap - nslots) * sizeof(DetRec) +
-                         (size_t)nslots * (10 * 8 + 5 * 4 + 6 * 4 + 2 * 4) + path + 4096;
+                         (size_t)nslots * (13 * 8 + 5 * 4 + 6 * 4 + 2 * 4) + path + 4096;
     if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolPath == (path > 0) && c->poolDetPair == detPair)
         return SKIRT_OK;
     c->poolPath = path > 0;
@@ -3475,7 +3616,7 @@ void carvePool(SkirtMcrt* c, Args& a) {
     a.det = reinterpret_cast<DetRec*>(p);  // at most one peel-off per instrument and slot per iteration
     p += (c->poolDetPair ? 2 : 1) * (size_t)(c->rayCap - c->nslots) * sizeof(DetRec);
     takeD(a.srx); takeD(a.sry); takeD(a.srz); takeD(a.skx); takeD(a.sky); takeD(a.skz); takeD(a.sL); takeD(a.sLth);
-    takeD(a.resA); takeD(a.resB);
+    takeD(a.resA); takeD(a.resB); takeD(a.resS); takeD(a.fuseU); takeD(a.fuseThr);
     takeI(a.sell); takeI(a.snscatt); takeI(a.sstellar); takeI(a.sstate); takeI(a.svcell);
     takeU(a.splo); takeU(a.sphi); takeU(a.sblock); takeU(a.sw2); takeU(a.sw3); takeU(a.shave);
     takeI(a.act[0]); takeI(a.act[1]);
@@ -4679,7 +4820,7 @@ static int planPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint
                      uint64_t sliceLo, uint64_t sliceCnt, uint64_t seed, const SkirtPhaseParams* p, PhasePlan& pl) {
     int rc;
     // slot pool: enough packets in flight to fill the chip many times over, bounded by the phase size.
-    // 2^24 slots (6.6 GB of packet state and ray queues with one instrument) make each iteration's trace
+    // 2^24 slots (7.0 GB of packet state and ray queues with one instrument) make each iteration's trace
     // launch long enough that its drain tail and the event kernel amortise (round 1, C3: 2^21 slots 1.87e8
     // pkt/s, 2^22 1.98e8, 2^23 2.04e8, 2^24 2.05e8; round 4 at the configurations' sizes, 2^24 against
     // 2^23: C3 +1.5 %, C2 +0.7 %, C4 +0.7 %, C5 +0.3 %, profiles/r04_slots_2e24.txt)
@@ -4743,6 +4884,10 @@ static int planPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint
     a.threshold = c->threshold > 0 ? c->threshold : (c->gridKind == SKIRT_GRID_VORONOI ? 8 : 16);
     a.walkBack = c->walkBack >= 0 ? c->walkBack : (c->gridKind == SKIRT_GRID_VORONOI ? 1 : 0);
     if ((rc = planLds(c, pl))) return rc;
+    // (the node-array walk's no-store kernel has no registers for the lane's decision, Tracer::kFuse)
+    a.fuse = (continuous || (pl.noStore && kind == kOctreeNodes)) ? 0
+             : c->fuseWalk >= 0                                    ? std::min(c->fuseWalk, 2)
+                                                                   : (c->gridKind == SKIRT_GRID_VORONOI ? 0 : 1);
     c->lastWalk = walkOf(kind).stat;
     pl.traceFn = traceKernelOf(kind, a.ncomp == 1, continuous, a.labsGlobal != 0, pl.noStore);
     if (pl.ldsTrace > 64 * 1024)
