@@ -1,6 +1,6 @@
 // The path of a ray through an axisymmetric R-z dust grid: Cylinder2DDustGrid::path
 // (SKIRTcore/Cylinder2DDustGrid.cpp:135-362) as an entry function and a step function, in the reference's f64
-// operations and order. The same text compiles for gfx950 (engine.hip, Grid<SKIRT_GRID_CYLINDER2D>) and as
+// operations and order. The same text compiles for gfx950 (grid_mesh2d.hpp, Grid<SKIRT_GRID_CYLINDER2D>) and as
 // plain C++ (tools/cyl2d_walk_cpu.py, the CPU logic test), so it touches nothing of the engine: borders come in
 // as plain arrays (LDS on the device), segments leave through a callable.
 //

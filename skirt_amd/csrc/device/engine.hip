@@ -51,15 +51,23 @@ constexpr int kSegWords = 3 * (kBlock / 64) * 4 / 8;  // the trace kernel's per-
 #define SKIRT_LABS_BUF 16
 #endif
 constexpr int kLabsBuf = SKIRT_LABS_BUF;  // buffered Labs adds per trace lane (LDS)
-#ifndef SKIRT_VOR_DRAIN2
-#define SKIRT_VOR_DRAIN2 1
-#endif
 constexpr int kStepsPerPull = 4;  // grid steps between two ray pulls of a trace wave
 // device counters of the pipeline (Args::ctr): 16, each on a 128-byte line of its own (kCtrStride words
 // apart). The event kernel's block reservations add to four of them every round; packed in one line, those
 // atomics serialized on it: C3 +2.1 %, C2 +6.9 %, C4 +0.5 % apart (profiles/r05_ctr_lines_ab.txt)
 constexpr int kCtrStride = 32;
-constexpr int kCtrWords = 16 * kCtrStride;
+// which counter is which. The ones "by parity" are pairs: + Args::parity is this iteration's, + 1 - parity the
+// next one's, which the kernels of this iteration already append to or reset
+enum Ctr : int {
+    CTR_RAYS = 0,      // by parity: rays queued from the bottom of the ray queue
+    CTR_ACTIVE = 2,    // by parity: entries of the active slot list Args::act
+    CTR_PULL = 4,      // the trace kernel's pull counter: queue ids handed out in this launch
+    CTR_DET = 5,       // by parity: detection records
+    CTR_RESERVED = 7,  // reserved
+    CTR_WALK = 8,      // by parity: WALK rays, queued from the top of the ray queue (Args::walkBack)
+    CTR_COUNT = 16     // 10 .. 15 reserved
+};
+constexpr int kCtrWords = CTR_COUNT * kCtrStride;
 #define CTR(base, k) ((base)[(k) * kCtrStride])
 #define CTRP(base, k) ((base) + (k) * kCtrStride)
 constexpr const char* kGeomCapMessage =
@@ -411,8 +419,7 @@ struct Args {
     DetRec* det;                 // detection records of the peel-off rays
     int* act[2];                 // active slot lists (double buffered)
     unsigned long long* claim;   // next packet index (relative to first)
-    unsigned int* ctr;           // [0,1] ray counts, [2,3] active counts, [4] trace pull counter,
-                                 // [5,6] detection record counts
+    unsigned int* ctr;           // the pipeline's counters (enum Ctr), through CTR / CTRP
     int parity, init, threshold;
     int walkBack;                // WALK rays queued from the top of the ray queue, so they are pulled last
     // continuous scattering: per slot the dust segments of its last FILL path and their number
@@ -580,1083 +587,12 @@ struct Ray {
 template <int GRID>
 struct Grid;
 
-// Cartesian grid: CartesianDustGrid.cpp:136-283 (mesh borders staged in LDS)
-template <>
-struct Grid<SKIRT_GRID_CARTESIAN> {
-    __device__ static __forceinline__ int locateClip(const double* v, int n, double q) {  // NR::locate_clip
-        if (q < v[0]) return 0;
-        int jl = -1, ju = n - 1;
-        while (ju - jl > 1) {
-            const int jm = (ju + jl) >> 1;
-            if (q < v[jm]) ju = jm;
-            else jl = jm;
-        }
-        return jl;
-    }
-    __device__ static __forceinline__ int locateFail(const double* v, int n, double q) {  // NR::locate_fail
-        if (q > v[n - 1]) return -1;
-        int jl = -1, ju = n - 1;
-        while (ju - jl > 1) {
-            const int jm = (ju + jl) >> 1;
-            if (q < v[jm]) ju = jm;
-            else jl = jm;
-        }
-        return jl;
-    }
-
-    // the entry part of the path: up to three segments outside the grid (m = -1), then the first cell;
-    // false for an empty path
-    template <class SegFn>
-    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        const double* xv = sh.mesh;
-        const double* yv = xv + a.nx + 1;
-        const double* zv = yv + a.ny + 1;
-        const double kx = r.dx, ky = r.dy, kz = r.dz;
-        double x = r.x, y = r.y, z = r.z, d0 = 0, d1 = 0, d2 = 0;
-        if (x < a.gx0) {
-            if (kx <= 0.0) return false;
-            d0 = (a.gx0 - x) / kx;
-            x = a.gx0 + 1e-8 * (xv[1] - xv[0]); y += ky * d0; z += kz * d0;
-        } else if (x > a.gx1) {
-            if (kx >= 0.0) return false;
-            d0 = (a.gx1 - x) / kx;
-            x = a.gx1 - 1e-8 * (xv[a.nx] - xv[a.nx - 1]); y += ky * d0; z += kz * d0;
-        }
-        if (y < a.gy0) {
-            if (ky <= 0.0) return false;
-            d1 = (a.gy0 - y) / ky;
-            x += kx * d1; y = a.gy0 + 1e-8 * (yv[1] - yv[0]); z += kz * d1;
-        } else if (y > a.gy1) {
-            if (ky >= 0.0) return false;
-            d1 = (a.gy1 - y) / ky;
-            x += kx * d1; y = a.gy1 - 1e-8 * (yv[a.ny] - yv[a.ny - 1]); z += kz * d1;
-        }
-        if (z < a.gz0) {
-            if (kz <= 0.0) return false;
-            d2 = (a.gz0 - z) / kz;
-            x += kx * d2; y += ky * d2; z = a.gz0 + 1e-8 * (zv[1] - zv[0]);
-        } else if (z > a.gz1) {
-            if (kz >= 0.0) return false;
-            d2 = (a.gz1 - z) / kz;
-            x += kx * d2; y += ky * d2; z = a.gz1 - 1e-8 * (zv[a.nz] - zv[a.nz - 1]);
-        }
-        if (x < a.gx0 || x > a.gx1 || y < a.gy0 || y > a.gy1 || z < a.gz0 || z > a.gz1) return false;
-        if (d0 > 0) seg(-1, 0.0, d0);
-        if (d1 > 0) seg(-1, 0.0, d1);
-        if (d2 > 0) seg(-1, 0.0, d2);
-        r.x = x; r.y = y; r.z = z;
-        r.ci = locateClip(xv, a.nx + 1, x);
-        r.cj = locateClip(yv, a.ny + 1, y);
-        r.ck = locateClip(zv, a.nz + 1, z);
-        r.rho0 = a.rho[(size_t)dev(a, r.ci, r.cj, r.ck) * a.ncomp];
-        return true;
-    }
-
-    // device number of cell (i, j, k). Bricked: the 8 cells of each 2x2x2 brick are consecutive and
-    // start on a 64-byte line of every Labs row (a ray crosses about 2.5 cells of a brick it enters,
-    // whose Labs adds then share one atomic request); bricks in the reference's (i, j, k) order.
-    // Unbricked: the reference's index k + Nz j + Nz Ny i (CartesianDustGrid.cpp:305-308).
-    __device__ static __forceinline__ int dev(const Args& a, int i, int j, int k) {
-        if (!a.brick) return k + a.nz * j + a.nz * a.ny * i;
-        const int by = (a.ny + 1) >> 1, bz = (a.nz + 1) >> 1;
-        return ((((i >> 1) * by + (j >> 1)) * bz + (k >> 1)) << 3) | ((i & 1) << 2) | ((j & 1) << 1) | (k & 1);
-    }
-
-    // one grid step: emits (m, ds); false when the ray ends (left the grid or stopped by seg)
-    template <class SegFn>
-    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        const double* xv = sh.mesh;
-        const double* yv = xv + a.nx + 1;
-        const double* zv = yv + a.ny + 1;
-        const int i = r.ci, j = r.cj, k = r.ck;
-        const int m = dev(a, i, j, k);
-        const double rho0 = r.rho0;  // loaded by the previous step (or begin), off this step's chain
-        const double xE = (r.dx < 0.0) ? xv[i] : xv[i + 1];
-        const double yE = (r.dy < 0.0) ? yv[j] : yv[j + 1];
-        const double zE = (r.dz < 0.0) ? zv[k] : zv[k + 1];
-        const double dsx = (r.ix != 0.0) ? (xE - r.x) * r.ix : kDblMax;
-        const double dsy = (r.iy != 0.0) ? (yE - r.y) * r.iy : kDblMax;
-        const double dsz = (r.iz != 0.0) ? (zE - r.z) * r.iz : kDblMax;
-        // the exit wall (the reference's order of comparisons), then one segment: lanes leaving through
-        // different walls share the segment code instead of running it once per wall
-        const bool ex = dsx <= dsy && dsx <= dsz;
-        const bool ey = !ex && dsy < dsx && dsy <= dsz;
-        const bool ez = !ex && !ey && dsz < dsx && dsz < dsy;
-        if (!(ex || ey || ez)) return false;  // NaN direction; the reference would loop forever
-        const double ds = ex ? dsx : ey ? dsy : dsz;
-        if (!seg(m, rho0, ds)) return false;
-        const int ni = i + (ex ? ((r.dx < 0.0) ? -1 : 1) : 0);
-        const int nj = j + (ey ? ((r.dy < 0.0) ? -1 : 1) : 0);
-        const int nk = k + (ez ? ((r.dz < 0.0) ? -1 : 1) : 0);
-        if (ni >= a.nx || ni < 0 || nj >= a.ny || nj < 0 || nk >= a.nz || nk < 0) return false;
-        r.ci = ni; r.cj = nj; r.ck = nk;
-        r.rho0 = a.rho[(size_t)dev(a, ni, nj, nk) * a.ncomp];  // the next step's density, requested now
-        r.x = ex ? xE : r.x + r.dx * ds;
-        r.y = ey ? yE : r.y + r.dy * ds;
-        r.z = ez ? zE : r.z + r.dz * ds;
-        return true;
-    }
-
-    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
-        const double* xv = sh.mesh;
-        const double* yv = xv + a.nx + 1;
-        const double* zv = yv + a.ny + 1;
-        const int i = locateFail(xv, a.nx + 1, x), j = locateFail(yv, a.ny + 1, y), k = locateFail(zv, a.nz + 1, z);
-        if (i < 0 || j < 0 || k < 0) return -1;
-        return dev(a, i, j, k);
-    }
-};
-
-// Axisymmetric R-z grid: Cylinder2DDustGrid.cpp:135-362 through device/cyl2d_walk.hpp (the walk's arithmetic,
-// shared with the CPU logic test). The borders R | (one unused word, ny = 0) | z are staged in LDS like the
-// Cartesian mesh; device cell number = reference cell number k + nz i, so the cells of one radial shell that
-// are adjacent in z share Labs lines. The walk's state lives in registers the Cartesian walk leaves unused:
-// q, p, k_q, k_z, q_N in bx0, by0, bz0, bx1, by1; z in r.z; i, i_min, k in ci, cj, ck; inward in jx.
-template <>
-struct Grid<SKIRT_GRID_CYLINDER2D> {
-    __device__ static __forceinline__ const double* zBorders(const Args& a, const Shared& sh) {
-        return sh.mesh + a.nx + 1 + a.ny + 1;
-    }
-    __device__ static __forceinline__ Cyl2dState get(const Ray& r) {
-        return Cyl2dState{r.bx0, r.z, r.by0, r.bz0, r.bx1, r.by1, r.ci, r.ck, r.cj, r.jx};
-    }
-    __device__ static __forceinline__ void put(Ray& r, const Cyl2dState& s) {
-        r.bx0 = s.q; r.z = s.z; r.by0 = s.p; r.bz0 = s.kq; r.bx1 = s.kz; r.by1 = s.qN;
-        r.ci = s.i; r.ck = s.k; r.cj = s.imin; r.jx = s.inward;
-    }
-    __device__ static __forceinline__ int dev(const Args& a, int i, int k) { return k + a.nz * i; }
-
-    // the entry part of the path: the segments outside the grid (m = -1), then the first cell; false for an
-    // empty path
-    template <class SegFn>
-    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        Cyl2dState s;
-        if (!cyl2dEnter(sh.mesh, a.nx, zBorders(a, sh), a.nz, r.x, r.y, r.z, r.dx, r.dy, r.dz, s,
-                        [&](int m, double ds) { seg(m, 0.0, ds); }))
-            return false;
-        put(r, s);
-        r.rho0 = a.rho[(size_t)dev(a, s.i, s.k) * a.ncomp];
-        return true;
-    }
-
-    // one grid step: emits (m, ds); false when the ray ends (left the grid or stopped by seg)
-    template <class SegFn>
-    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        Cyl2dState s = get(r);
-        const double rho0 = r.rho0;  // loaded by the previous step (or begin), off this step's chain
-        int m;
-        double ds;
-        const bool more = cyl2dStep(sh.mesh, a.nx, zBorders(a, sh), a.nz, s, m, ds);
-        if (!seg(m, rho0, ds) || !more) return false;
-        put(r, s);
-        r.rho0 = a.rho[(size_t)dev(a, s.i, s.k) * a.ncomp];  // the next step's density, requested now
-        return true;
-    }
-
-    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
-        return cyl2dWhichCell(sh.mesh, a.nx, zBorders(a, sh), a.nz, x, y, z);
-    }
-};
-
-// Spherical shells: Sphere1DDustGrid.cpp:111-187 through device/sph_walk.hpp. The borders r (then two unused
-// words, ny = nz = 0) are staged in LDS like the Cartesian mesh; r_max = maxR() travels in gx1 (a LogMesh's last
-// border may miss it by a bit); device cell number = shell number. State: q, p, q_N in bx0, by0, bz0; i, i_min in
-// ci, cj; inward in jx. i moves monotonically in each part of the walk, so a path has at most 2 N_r steps.
-template <>
-struct Grid<SKIRT_GRID_SPHERE1D> {
-    __device__ static __forceinline__ Sph1dState get(const Ray& r) {
-        return Sph1dState{r.bx0, r.by0, r.bz0, r.ci, r.cj, r.jx};
-    }
-    __device__ static __forceinline__ void put(Ray& r, const Sph1dState& s) {
-        r.bx0 = s.q; r.by0 = s.p; r.bz0 = s.qN; r.ci = s.i; r.cj = s.imin; r.jx = s.inward;
-    }
-    __device__ static __forceinline__ int dev(const Args&, int i) { return i; }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        Sph1dState s;
-        if (!sph1dEnter(sh.mesh, a.nx, a.gx1, r.x, r.y, r.z, r.dx, r.dy, r.dz, s,
-                        [&](int m, double ds) { seg(m, 0.0, ds); }))
-            return false;
-        put(r, s);
-        r.rho0 = a.rho[(size_t)s.i * a.ncomp];
-        return true;
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        Sph1dState s = get(r);
-        const double rho0 = r.rho0;  // loaded by the previous step (or begin), off this step's chain
-        int m;
-        double ds;
-        const bool more = sph1dStep(sh.mesh, a.nx, s, m, ds);
-        if (!seg(m, rho0, ds) || !more) return false;
-        put(r, s);
-        r.rho0 = a.rho[(size_t)s.i * a.ncomp];  // the next step's density, requested now
-        return true;
-    }
-
-    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
-        return sph1dWhichCell(sh.mesh, a.nx, x, y, z);
-    }
-};
-
-// Shells x polar bins: Sphere2DDustGrid.cpp:186-359 through device/sph_walk.hpp. The borders r | cos theta | theta
-// (nx = N_r, ny = nz = N_theta) are staged in LDS in the mesh layout; r_max in gx1, eps = 1e-11 r_max in a.eps;
-// device cell number = reference cell number k + N_theta i. The position advances in r.x, r.y, r.z; i, k in ci,
-// ck; the steps the path may still take (sph2dStepCap) in cj. A step that finds no exit nudges the position and
-// emits no segment (m = -1, ds = 0).
-template <>
-struct Grid<SKIRT_GRID_SPHERE2D> {
-    __device__ static __forceinline__ const double* cosBorders(const Args& a, const Shared& sh) {
-        return sh.mesh + a.nx + 1;
-    }
-    __device__ static __forceinline__ const double* thetaBorders(const Args& a, const Shared& sh) {
-        return sh.mesh + a.nx + 1 + a.ny + 1;
-    }
-    __device__ static __forceinline__ int dev(const Args& a, int i, int k) { return k + a.nz * i; }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        Sph2dState s;
-        if (!sph2dEnter(sh.mesh, a.nx, thetaBorders(a, sh), a.nz, a.gx1, a.eps, r.x, r.y, r.z, r.dx, r.dy, r.dz, s,
-                        [&](int m, double ds) { seg(m, 0.0, ds); }))
-            return false;
-        r.x = s.x; r.y = s.y; r.z = s.z; r.ci = s.i; r.ck = s.k; r.cj = s.left;
-        r.rho0 = a.rho[(size_t)dev(a, s.i, s.k) * a.ncomp];
-        return true;
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        Sph2dState s{r.x, r.y, r.z, r.ci, r.ck, r.cj};
-        const double rho0 = r.rho0;  // loaded by the previous step (or begin), off this step's chain
-        int m;
-        double ds;
-        const bool more = sph2dStep(sh.mesh, a.nx, cosBorders(a, sh), thetaBorders(a, sh), a.nz, a.eps, r.dx, r.dy,
-                                    r.dz, s, m, ds);
-        if (!seg(m, rho0, ds) || !more) return false;
-        r.x = s.x; r.y = s.y; r.z = s.z; r.ci = s.i; r.ck = s.k; r.cj = s.left;
-        r.rho0 = a.rho[(size_t)dev(a, s.i, s.k) * a.ncomp];  // the next step's density, requested now
-        return true;
-    }
-
-    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
-        return sph2dWhichCell(sh.mesh, a.nx, thetaBorders(a, sh), a.nz, x, y, z);
-    }
-};
-
-// Octree grid walked through the node arrays: TreeDustGrid.cpp:390-521 (TopDown and Neighbor
-// search), DustGridPath::moveInside. Used for trees the leaf map cannot hold, and by the leaf-map
-// walk below for the rare steps whose exit point lies on a cell face.
-template <>
-struct Grid<kOctreeNodes> {
-    __device__ static __forceinline__ void loadBox(const Args& a, int l, double& x0, double& y0, double& z0,
-                                                   double& x1, double& y1, double& z1) {
-        const double2* b = reinterpret_cast<const double2*>(a.box + 6 * (size_t)l);
-        const double2 p = b[0], q = b[1], w = b[2];
-        x0 = p.x; y0 = p.y; z0 = q.x; x1 = q.y; y1 = w.x; z1 = w.y;
-    }
-
-    // TreeNode::whichnode from the root + OctTreeNode::child(r) / BinTreeNode::child(r)
-    // (BinTreeNode.cpp:322-331): the leaf containing (x,y,z) or -1
-    __device__ static __forceinline__ int descend(const Args& a, double x, double y, double z) {
-        if (!(x >= a.gx0 && x <= a.gx1 && y >= a.gy0 && y <= a.gy1 && z >= a.gz0 && z <= a.gz1)) return -1;
-        int l = 0;
-        int c0 = a.firstChild[0];
-        while (c0 >= 0) {
-            const double* cb = a.box + 6 * (size_t)c0 + 3;  // split point = rmax of child 0
-            if (a.splitDir) {
-                const int d = a.splitDir[l];
-                l = c0 + ((d == 0 ? x : d == 1 ? y : z) < cb[d] ? 0 : 1);
-            } else {
-                l = c0 + (x < cb[0] ? 0 : 1) + (y < cb[1] ? 0 : 2) + (z < cb[2] ? 0 : 4);
-            }
-            c0 = a.firstChild[l];
-        }
-        return l;
-    }
-
-    // the part of the path before the grid (TreeDustGrid.cpp:404-440): up to three segments outside the
-    // grid; on return (x,y,z) is the entry point. False for an empty path.
-    __device__ static __forceinline__ bool enterGrid(const Args& a, double& rx, double& ry, double& rz, double kx,
-                                                     double ky, double kz, double (&d)[3]) {
-        const double eps = a.eps;
-        d[0] = d[1] = d[2] = 0;
-        if (rx <= a.gx0) {
-            if (kx <= 0.0) return false;
-            d[0] = (a.gx0 - rx) / kx; rx = a.gx0 + eps; ry += ky * d[0]; rz += kz * d[0];
-        } else if (rx >= a.gx1) {
-            if (kx >= 0.0) return false;
-            d[0] = (a.gx1 - rx) / kx; rx = a.gx1 - eps; ry += ky * d[0]; rz += kz * d[0];
-        }
-        if (ry <= a.gy0) {
-            if (ky <= 0.0) return false;
-            d[1] = (a.gy0 - ry) / ky; rx += kx * d[1]; ry = a.gy0 + eps; rz += kz * d[1];
-        } else if (ry >= a.gy1) {
-            if (ky >= 0.0) return false;
-            d[1] = (a.gy1 - ry) / ky; rx += kx * d[1]; ry = a.gy1 - eps; rz += kz * d[1];
-        }
-        if (rz <= a.gz0) {
-            if (kz <= 0.0) return false;
-            d[2] = (a.gz0 - rz) / kz; rx += kx * d[2]; ry += ky * d[2]; rz = a.gz0 + eps;
-        } else if (rz >= a.gz1) {
-            if (kz >= 0.0) return false;
-            d[2] = (a.gz1 - rz) / kz; rx += kx * d[2]; ry += ky * d[2]; rz = a.gz1 - eps;
-        }
-        return true;
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool begin(const Args& a, const Shared&, Ray& r, SegFn seg) {
-        double rx = r.x, ry = r.y, rz = r.z, d[3];
-        if (!enterGrid(a, rx, ry, rz, r.dx, r.dy, r.dz, d)) return false;
-        const int node = descend(a, rx, ry, rz);
-        if (node < 0) return false;
-        for (int q = 0; q < 3; q++)
-            if (d[q] > 0) seg(-1, 0.0, d[q]);
-        r.x = rx; r.y = ry; r.z = rz;
-        r.ci = node;
-        r.cj = a.cellnumber[node];
-        loadBox(a, node, r.bx0, r.by0, r.bz0, r.bx1, r.by1, r.bz1);
-        return true;
-    }
-
-    // the node after `node` for a ray leaving it through `wall` at (x,y,z) (already advanced by
-    // ds + eps): TreeNode::whichnode(wall, r) over the sorted neighbour list, else the descent from the
-    // root, with the reference's nextafter escape when the point has not left the node. May move
-    // (x,y,z). Returns -1 when the path leaves the grid.
-    __device__ static __forceinline__ int nextNode(const Args& a, int node, int wall, double& x, double& y, double& z,
-                                                   double kx, double ky, double kz) {
-        if (a.search == SKIRT_TREE_NEIGHBOR) {
-            const int q = 6 * node + wall;
-            const int nb = a.nbrOffset[q], ne = a.nbrOffset[q + 1];
-            for (int n = nb; n < ne; n++) {
-                const int c = a.nbrList[n];
-                double x0, y0, z0, x1, y1, z1;
-                loadBox(a, c, x0, y0, z0, x1, y1, z1);
-                if (x >= x0 && x <= x1 && y >= y0 && y <= y1 && z >= z0 && z <= z1) return c;
-            }
-        }
-        int next = descend(a, x, y, z);
-        if (next == node) {
-            // stuck: advance to the next representable coordinates (TreeDustGrid.cpp:502-519)
-            x = nextafter(x, (kx < 0.0) ? -kDblMax : kDblMax);
-            y = nextafter(y, (ky < 0.0) ? -kDblMax : kDblMax);
-            z = nextafter(z, (kz < 0.0) ? -kDblMax : kDblMax);
-            next = descend(a, x, y, z);
-            if (next == node) return -1;
-        }
-        return next;
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool step(const Args& a, const Shared&, Ray& r, SegFn seg) {
-        const int node = r.ci;
-        const double xnext = (r.dx < 0.0) ? r.bx0 : r.bx1;
-        const double ynext = (r.dy < 0.0) ? r.by0 : r.by1;
-        const double znext = (r.dz < 0.0) ? r.bz0 : r.bz1;
-        const double dsx = (r.ix != 0.0) ? (xnext - r.x) * r.ix : kDblMax;
-        const double dsy = (r.iy != 0.0) ? (ynext - r.y) * r.iy : kDblMax;
-        const double dsz = (r.iz != 0.0) ? (znext - r.z) * r.iz : kDblMax;
-        double ds;
-        int wall;
-        if (dsx <= dsy && dsx <= dsz) { ds = dsx; wall = (r.dx < 0.0) ? 0 : 1; }
-        else if (dsy <= dsx && dsy <= dsz) { ds = dsy; wall = (r.dy < 0.0) ? 2 : 3; }
-        else { ds = dsz; wall = (r.dz < 0.0) ? 4 : 5; }
-        if (!seg(r.cj, a.rho[(size_t)r.cj * a.ncomp], ds)) return false;
-        double x = r.x + (ds + a.eps) * r.dx;
-        double y = r.y + (ds + a.eps) * r.dy;
-        double z = r.z + (ds + a.eps) * r.dz;
-        const int next = nextNode(a, node, wall, x, y, z, r.dx, r.dy, r.dz);
-        if (next < 0) return false;
-        loadBox(a, next, r.bx0, r.by0, r.bz0, r.bx1, r.by1, r.bz1);
-        r.x = x; r.y = y; r.z = z;
-        r.ci = next;
-        r.cj = a.cellnumber[next];
-        return true;
-    }
-
-
-    __device__ static __forceinline__ int whichcell(const Args& a, const Shared&, double x, double y, double z) {
-        const int l = descend(a, x, y, z);
-        return l < 0 ? -1 : a.cellnumber[l];
-    }
-};
-
-// Octree grid, Bookkeeping search (TreeDustGrid.cpp:523-659): the next node follows from the breadth-first
-// numbering (the 8 children of a node are consecutive ids in octant order, so (l-1) % 8 is the octant of
-// node l): climb while the node lies on the far side of its father, step to the sibling across the wall,
-// descend with "<=" to the leaf holding the exit point. The position is put on the crossed wall exactly
-// (no eps). Entry into the grid as for the other searches.
-template <>
-struct Grid<kOctreeBookkeeping> {
-    using Nodes = Grid<kOctreeNodes>;
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        return Nodes::begin(a, sh, r, seg);
-    }
-    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
-        return Nodes::whichcell(a, sh, x, y, z);
-    }
-
-    __device__ static __forceinline__ const double* childBox(const Args& a, int l) {
-        return a.box + 6 * (size_t)a.firstChild[l];
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool step(const Args& a, const Shared&, Ray& r, SegFn seg) {
-        const double xnext = (r.dx < 0.0) ? r.bx0 : r.bx1;
-        const double ynext = (r.dy < 0.0) ? r.by0 : r.by1;
-        const double znext = (r.dz < 0.0) ? r.bz0 : r.bz1;
-        const double dsx = (r.ix != 0.0) ? (xnext - r.x) * r.ix : kDblMax;
-        const double dsy = (r.iy != 0.0) ? (ynext - r.y) * r.iy : kDblMax;
-        const double dsz = (r.iz != 0.0) ? (znext - r.z) * r.iz : kDblMax;
-        int l = r.ci;
-        if (dsx <= dsy && dsx <= dsz) {
-            if (!seg(r.cj, a.rho[(size_t)r.cj * a.ncomp], dsx)) return false;
-            r.x = xnext; r.y += r.dy * dsx; r.z += r.dz * dsx;
-            while ((r.dx < 0.0) ? (((l - 1) & 1) == 0) : (((l - 1) & 1) == 1)) {
-                l = a.father[l];
-                if (l == 0) return false;
-            }
-            l += (r.dx < 0.0) ? -1 : 1;
-            while (a.cellnumber[l] < 0) {
-                const double* cb = childBox(a, l);
-                const int k = (r.dx < 0.0 ? 1 : 0) + (r.y <= cb[4] ? 0 : 2) + (r.z <= cb[5] ? 0 : 4);
-                l = a.firstChild[l] + k;
-            }
-        } else if (dsy < dsx && dsy <= dsz) {
-            if (!seg(r.cj, a.rho[(size_t)r.cj * a.ncomp], dsy)) return false;
-            r.x += r.dx * dsy; r.y = ynext; r.z += r.dz * dsy;
-            while ((r.dy < 0.0) ? (((l - 1) & 2) == 0) : (((l - 1) & 2) != 0)) {
-                l = a.father[l];
-                if (l == 0) return false;
-            }
-            l += (r.dy < 0.0) ? -2 : 2;
-            while (a.cellnumber[l] < 0) {
-                const double* cb = childBox(a, l);
-                const int k = (r.x <= cb[3] ? 0 : 1) + (r.dy < 0.0 ? 2 : 0) + (r.z <= cb[5] ? 0 : 4);
-                l = a.firstChild[l] + k;
-            }
-        } else if (dsz < dsx && dsz < dsy) {
-            if (!seg(r.cj, a.rho[(size_t)r.cj * a.ncomp], dsz)) return false;
-            r.x += r.dx * dsz; r.y += r.dy * dsz; r.z = znext;
-            while ((r.dz < 0.0) ? (((l - 1) & 4) == 0) : (((l - 1) & 4) != 0)) {
-                l = a.father[l];
-                if (l == 0) return false;
-            }
-            l += (r.dz < 0.0) ? -4 : 4;
-            while (a.cellnumber[l] < 0) {
-                const double* cb = childBox(a, l);
-                const int k = (r.x <= cb[3] ? 0 : 1) + (r.y <= cb[4] ? 0 : 2) + (r.dz < 0.0 ? 4 : 0);
-                l = a.firstChild[l] + k;
-            }
-        } else {
-            return false;  // NaN distances
-        }
-        r.ci = l;
-        r.cj = a.cellnumber[l];
-        Nodes::loadBox(a, l, r.bx0, r.by0, r.bz0, r.bx1, r.by1, r.bz1);
-        return true;
-    }
-};
-
-// Octree grid through the leaf map. An octree split at box centres (OctTreeNode::createchildren,
-// OctTreeNode.cpp:53-56, Box::center) has, per axis, one table of 2^L + 1 split coordinates T (L the
-// deepest level) such that a level-l node with integer coordinate i spans [T[i << (L-l)],
-// T[(i+1) << (L-l)]] -- bit for bit, since every split is 0.5*(lo+hi) of two table entries. So:
-//   - the box faces come from the T tables in LDS (no box gather);
-//   - the leaf containing a point is the leaf map entry of the finest-level cell holding it: one
-//     16-byte load instead of the neighbour-list walk. Locating by "T[j] <= x < T[j+1]" is exactly
-//     the reference's root descent (x < split -> lower child), so the only steps where it can differ
-//     from the inclusive-box neighbour search (TreeNode::whichnode(wall, r)) are those whose exit point
-//     lies exactly on a lower face of the leaf found, or that have not left the current leaf; those
-//     take the node-array search above. The walk is therefore the reference's, step for step.
-// The host builds the map only after checking every node box against the T tables.
-// A k-d tree (BinTreeNode::createchildren_splitdir also halves at the centre, one axis at a time) maps
-// the same way with per-axis leaf extents (BIN): its entries carry the three shifts instead of a level.
-template <bool BIN>
-struct LeafMapGrid {
-    using Nodes = Grid<kOctreeNodes>;
-
-    // a leaf's extent along x, y, z in finest cells, as shifts
-    __device__ static __forceinline__ void shifts(const Args& a, unsigned cl, int& sx, int& sy, int& sz) {
-        if (BIN) {
-            const unsigned s = cl >> kBinCellBits;
-            sx = (int)(s & 7u); sy = (int)((s >> 3) & 7u); sz = (int)((s >> 6) & 7u);
-        } else {
-            sx = sy = sz = a.mapL - (int)(cl >> kLeafLevelShift);
-        }
-    }
-    __device__ static __forceinline__ int cellOf(unsigned cl) { return (int)(cl & (BIN ? kBinCellMask : kLeafCellMask)); }
-
-    // finest-level index j with T[j] <= v < T[j+1] (the last cell also holds v == T[N]); v in [T[0], T[N]].
-    // The split coordinates are uniform to rounding, so the estimate is off by one at most near a
-    // split; the loops only run for that rare lane.
-    __device__ static __forceinline__ int estimate(int N, double t0, double inv, double v) {
-        return max(0, min(N - 1, (int)((v - t0) * inv)));
-    }
-    __device__ static __forceinline__ int correct(const double* T, int N, int j, double v) {
-        const double lo = T[j], hi = T[j + 1];
-        if (v < lo) {
-            do j--; while (j > 0 && v < T[j]);
-            j = max(j, 0);  // v below T[0]: a point outside the grid, whose entry is fetched but not used
-        } else if (v >= hi && j < N - 1) {
-            do j++; while (j < N - 1 && v >= T[j + 1]);
-        }
-        return j;
-    }
-
-    __device__ static __forceinline__ bool inside(const Args& a, double x, double y, double z) {
-        return x >= a.gx0 && x <= a.gx1 && y >= a.gy0 && y <= a.gy1 && z >= a.gz0 && z <= a.gz1;
-    }
-
-    // issues the load of the leaf map entry of the point (clamped into the grid, so any point -- even
-    // NaN -- reads a valid entry); fx, fy, fz its finest-level indices. The entry of the estimated cell
-    // is requested before the estimate is checked against the T tables in LDS; the rare lane whose
-    // estimate was off by one requests the right entry again.
-    __device__ static __forceinline__ int4 fetch(const Args& a, const Shared& sh, double x, double y, double z,
-                                                 int& fx, int& fy, int& fz) {
-        const int N = a.mapN;
-        const double* tx = sh.mesh;
-        const int ex = estimate(N, a.mapX0, a.mapInvX, x);
-        const int ey = estimate(N, a.mapY0, a.mapInvY, y);
-        const int ez = estimate(N, a.mapZ0, a.mapInvZ, z);
-        int4 v = *reinterpret_cast<const int4*>(a.leafMap + leafIndex(N, ex, ey, ez));
-        fx = correct(tx, N, ex, x);
-        fy = correct(tx + (N + 1), N, ey, y);
-        fz = correct(tx + 2 * (N + 1), N, ez, z);
-        if (fx != ex || fy != ey || fz != ez) v = *reinterpret_cast<const int4*>(a.leafMap + leafIndex(N, fx, fy, fz));
-        return v;
-    }
-
-    __device__ static __forceinline__ LeafEntry decode(int4 v) {
-        // one 16-byte load: keep the compiler from splitting off the density into a later second load
-        asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
-        LeafEntry e;
-        e.node = v.x;
-        e.cl = (unsigned)v.y;
-        const long long bits = ((long long)(unsigned)v.w << 32) | (unsigned)v.z;
-        e.rho0 = __longlong_as_double(bits);
-        return e;
-    }
-
-    // leaf map entry of the point (inside the grid); fx, fy, fz its finest-level indices
-    __device__ static __forceinline__ LeafEntry lookup(const Args& a, const Shared& sh, double x, double y, double z,
-                                                       int& fx, int& fy, int& fz) {
-        return decode(fetch(a, sh, x, y, z, fx, fy, fz));
-    }
-
-    // r.ck: the leaf's size in finest cells (octree) or its packed shifts (k-d tree); r.bx0, r.by0,
-    // r.bz0: the leaf's faces the ray leaves through along x, y, z (read from the T tables once, when
-    // the leaf is entered, so the next step starts without an LDS round trip)
-    __device__ static __forceinline__ void enterPlanes(Ray& r, int jx, int jy, int jz, const LeafEntry& e,
-                                                       double lox, double loy, double loz,
-                                                       double hix, double hiy, double hiz) {
-        r.ci = e.node;
-        r.cj = cellOf(e.cl);
-        if (BIN) r.ck = (int)(e.cl >> kBinCellBits);
-        r.jx = jx; r.jy = jy; r.jz = jz;
-        r.rho0 = e.rho0;
-        r.bx0 = (r.dx < 0.0) ? lox : hix;
-        r.by0 = (r.dy < 0.0) ? loy : hiy;
-        r.bz0 = (r.dz < 0.0) ? loz : hiz;
-    }
-    __device__ static __forceinline__ void enter(const Args& a, const Shared& sh, Ray& r, int fx, int fy, int fz,
-                                                 const LeafEntry& e) {
-        const int N1 = a.mapN + 1;
-        const double* tx = sh.mesh;
-        int sx, sy, sz;
-        shifts(a, e.cl, sx, sy, sz);
-        const int jx = (fx >> sx) << sx, jy = (fy >> sy) << sy, jz = (fz >> sz) << sz;
-        enterPlanes(r, jx, jy, jz, e, tx[jx], tx[N1 + jy], tx[2 * N1 + jz], tx[jx + (1 << sx)],
-                    tx[N1 + jy + (1 << sy)], tx[2 * N1 + jz + (1 << sz)]);
-        if (!BIN) r.ck = 1 << sx;
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool begin(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        double rx = r.x, ry = r.y, rz = r.z, d[3];
-        if (!Nodes::enterGrid(a, rx, ry, rz, r.dx, r.dy, r.dz, d)) return false;
-        if (!inside(a, rx, ry, rz)) return false;  // the root descent finds no node
-        for (int q = 0; q < 3; q++)
-            if (d[q] > 0) seg(-1, 0.0, d[q]);
-        int fx, fy, fz;
-        const LeafEntry e = lookup(a, sh, rx, ry, rz, fx, fy, fz);
-        r.x = rx; r.y = ry; r.z = rz;
-        enter(a, sh, r, fx, fy, fz, e);
-        prefetch(a, r);
-        return true;
-    }
-
-    // the exit of the current leaf: the distance to the nearest of its three faces ahead of the ray, the wall
-    // (the reference's order of comparisons) and the exit point nudged by eps
-    __device__ static __forceinline__ void exitPoint(const Args& a, const Ray& r, double& ds, int& wall, double& x,
-                                                     double& y, double& z) {
-        const double xnext = r.bx0, ynext = r.by0, znext = r.bz0;
-        const double dsx = (r.ix != 0.0) ? (xnext - r.x) * r.ix : kDblMax;
-        const double dsy = (r.iy != 0.0) ? (ynext - r.y) * r.iy : kDblMax;
-        const double dsz = (r.iz != 0.0) ? (znext - r.z) * r.iz : kDblMax;
-        if (dsx <= dsy && dsx <= dsz) { ds = dsx; wall = (r.dx < 0.0) ? 0 : 1; }
-        else if (dsy <= dsx && dsy <= dsz) { ds = dsy; wall = (r.dy < 0.0) ? 2 : 3; }
-        else { ds = dsz; wall = (r.dz < 0.0) ? 4 : 5; }
-        x = r.x + (ds + a.eps) * r.dx;
-        y = r.y + (ds + a.eps) * r.dy;
-        z = r.z + (ds + a.eps) * r.dz;
-    }
-
-    // requests the leaf-map entry of the estimated finest cell of the next exit point: issued at the end of a
-    // step, before the wave's Labs drain, it is in flight during the drain and the next step's segment. A load
-    // waits for every older vector-memory operation of its wave (vmcnt counts in issue order, atomics
-    // included, and a no-return f64 atomic stays counted for thousands of cycles under load): requested
-    // after the drain, each step's entry would wait for the previous step's Labs atomic too.
-    __device__ static __forceinline__ void prefetch(const Args& a, Ray& r) {
-        exitPoint(a, r, r.eds, r.ewall, r.ex, r.ey, r.ez);  // (kept for the step: the ray does not move before it)
-        const int N = a.mapN;
-        r.pfx = estimate(N, a.mapX0, a.mapInvX, r.ex);
-        r.pfy = estimate(N, a.mapY0, a.mapInvY, r.ey);
-        r.pfz = estimate(N, a.mapZ0, a.mapInvZ, r.ez);
-        r.pre = *reinterpret_cast<const int4*>(a.leafMap + leafIndex(N, r.pfx, r.pfy, r.pfz));
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        const int N1 = a.mapN + 1;
-        const double* tx = sh.mesh;
-        const double* ty = tx + N1;
-        const double* tz = ty + N1;
-        // the exit point prefetch computed at the end of the last step (or at the grid entry): 139 -> 129 VGPRs,
-        // C3 within the spread, C5 +0.5 % (profiles/r05_exit_reuse_ab.txt)
-        const double ds = r.eds;
-        double x = r.ex, y = r.ey, z = r.ez;
-        const int wall = r.ewall;
-        // the next leaf's entry is requested first; the segment's own work (optical depth, absorption)
-        // runs while the load is in flight
-        // the entry of the estimated finest cell; its leaf is the right one when the leaf's own faces
-        // (read anyway) contain the point, since T is monotone: then the exact finest cell lies in it too
-        const int N = a.mapN;
-        // requested by the previous step (prefetch), for the same exit point computed the same way
-        int fx = r.pfx, fy = r.pfy, fz = r.pfz;
-        const int4 raw = r.pre;
-        if (!seg(r.cj, r.rho0, ds)) return false;
-        if (!inside(a, x, y, z)) return false;  // no neighbour and no root descent contains it
-        LeafEntry e = decode(raw);
-        int lx, ly, lz;
-        shifts(a, e.cl, lx, ly, lz);
-        int jx = (fx >> lx) << lx, jy = (fy >> ly) << ly, jz = (fz >> lz) << lz;
-        // the new leaf's six faces in one LDS round trip: the lower ones decide whether the exit point
-        // lies on a face, the ones ahead of the ray are the next step's exit planes
-        double lox = tx[jx], loy = ty[jy], loz = tz[jz];
-        double hix = tx[jx + (1 << lx)], hiy = ty[jy + (1 << ly)], hiz = tz[jz + (1 << lz)];
-        if (!(x >= lox && x < hix && y >= loy && y < hiy && z >= loz && z < hiz)) {
-            // the estimate fell into a neighbouring leaf (or the point is on the grid's far faces): the
-            // exact finest cell, its entry and its leaf's faces
-            fx = correct(tx, N, fx, x);
-            fy = correct(ty, N, fy, y);
-            fz = correct(tz, N, fz, z);
-            e = decode(*reinterpret_cast<const int4*>(a.leafMap + leafIndex(N, fx, fy, fz)));
-            shifts(a, e.cl, lx, ly, lz);
-            jx = (fx >> lx) << lx; jy = (fy >> ly) << ly; jz = (fz >> lz) << lz;
-            lox = tx[jx]; loy = ty[jy]; loz = tz[jz];
-            hix = tx[jx + (1 << lx)]; hiy = ty[jy + (1 << ly)]; hiz = tz[jz + (1 << lz)];
-        }
-        r.x = x; r.y = y; r.z = z;
-        if (e.node == r.ci || x == lox || y == loy || z == loz) {
-            // on a face, or not out of the current leaf: the reference's own search decides
-            const int next = Nodes::nextNode(a, r.ci, wall, x, y, z, r.dx, r.dy, r.dz);
-            if (next < 0) return false;
-            const double* b = a.box + 6 * (size_t)next;  // its lower corner is a finest cell of it
-            e = lookup(a, sh, b[0], b[1], b[2], fx, fy, fz);
-            enter(a, sh, r, fx, fy, fz, e);
-            prefetch(a, r);
-            return true;
-        }
-        enterPlanes(r, jx, jy, jz, e, lox, loy, loz, hix, hiy, hiz);
-        if (!BIN) r.ck = 1 << lx;
-        prefetch(a, r);
-        return true;
-    }
-
-    __device__ static __forceinline__ int whichcell(const Args& a, const Shared& sh, double x, double y, double z) {
-        if (!inside(a, x, y, z)) return -1;
-        int fx, fy, fz;
-        return cellOf(lookup(a, sh, x, y, z, fx, fy, fz).cl);
-    }
-};
-
-template <>
-struct Grid<SKIRT_GRID_OCTREE> : LeafMapGrid<false> {};
-template <>
-struct Grid<kBinTreeMap> : LeafMapGrid<true> {};
-
-// Voronoi grid: VoronoiMesh::path (VoronoiMesh.cpp:749-844), cellIndex (:512-541), with the
-// reference's arithmetic order (bisector plane through the midpoint, Vec::dot left to right)
-template <>
-struct Grid<SKIRT_GRID_VORONOI> {
-    __device__ static __forceinline__ bool inside(const Args& a, double x, double y, double z) {
-        return x >= a.gx0 && x <= a.gx1 && y >= a.gy0 && y <= a.gy1 && z >= a.gz0 && z <= a.gz1;
-    }
-
-    // the cell whose site is nearest, over the cells listed for the point's block (Box::cellindices)
-    __device__ static __forceinline__ int cellIndex(const Args& a, double x, double y, double z) {
-        if (!inside(a, x, y, z)) return -1;
-        const int nb = a.vnb;
-        const int i = max(0, min(nb - 1, static_cast<int>(nb * (x - a.gx0) / (a.gx1 - a.gx0))));
-        const int j = max(0, min(nb - 1, static_cast<int>(nb * (y - a.gy0) / (a.gy1 - a.gy0))));
-        const int k = max(0, min(nb - 1, static_cast<int>(nb * (z - a.gz0) / (a.gz1 - a.gz0))));
-        const int b = i * nb * nb + j * nb + k;
-        int m = -1;
-        double best = kDblMax;
-        // the list in groups of kCellIndexGroup candidates, each {site, cell} in one 32-byte record, a group's
-        // records loaded together (one round trip per group); the candidates are then taken in list order, so
-        // the first of equal distances wins as in the reference's loop
-        constexpr int G = kCellIndexGroup;
-        const int qe = a.blockOffset[b + 1];
-        for (int q0 = a.blockOffset[b]; q0 < qe; q0 += G) {
-            int c[G];
-            double sx[G], sy[G], sz[G];
-#pragma unroll
-            for (int u = 0; u < G; u++) {
-                c[u] = -1;
-                sx[u] = sy[u] = sz[u] = 0.0;
-                if (q0 + u < qe) {
-                    const double2* rec = reinterpret_cast<const double2*>(a.blockSites + q0 + u);
-                    const double2 r0 = rec[0], r1 = rec[1];
-                    sx[u] = r0.x; sy[u] = r0.y; sz[u] = r1.x;
-                    c[u] = (int)(unsigned)__double_as_longlong(r1.y);  // the id, in the low word
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < G; u++) {
-                const double dx = x - sx[u], dy = y - sy[u], dz = z - sz[u];
-                const double d = dx * dx + dy * dy + dz * dz;
-                if (c[u] >= 0 && d < best) { best = d; m = c[u]; }
-            }
-        }
-        return m;
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool begin(const Args& a, const Shared&, Ray& r, SegFn seg) {
-        int none = kNoCell;
-        return beginAt(a, r, none, seg);
-    }
-
-    // begin() with the cell of the ray's origin cached in `cell` (kNoCell: not known yet). A point strictly
-    // inside the grid enters where it is, whatever the direction (enterGrid moves nothing), so its cellIndex
-    // serves every ray from that position: the peel-offs and the FILL ray of one event, and the WALK ray
-    // that retraces the FILL ray's path in the next one. A point on or outside the grid's faces enters
-    // where its direction takes it, so it is located per ray and not cached.
-    template <class SegFn>
-    __device__ static __forceinline__ bool beginAt(const Args& a, Ray& r, int& cell, SegFn seg) {
-        double rx = r.x, ry = r.y, rz = r.z, d[3];
-        const bool strict = rx > a.gx0 && rx < a.gx1 && ry > a.gy0 && ry < a.gy1 && rz > a.gz0 && rz < a.gz1;
-        if (!Grid<kOctreeNodes>::enterGrid(a, rx, ry, rz, r.dx, r.dy, r.dz, d)) return false;
-        int m;
-        if (strict && cell != kNoCell) m = cell;
-        else {
-            m = cellIndex(a, rx, ry, rz);
-            if (strict) cell = m;
-        }
-        if (m < 0) return false;
-        for (int q = 0; q < 3; q++)
-            if (d[q] > 0) seg(-1, 0.0, d[q]);
-        r.x = rx; r.y = ry; r.z = rz;
-        r.ci = m;
-        r.cj = a.vorStart[m];
-        r.ck = 0;
-        return true;
-    }
-
-    __device__ static __forceinline__ double wallDist(const Args& a, const Ray& r, int w) {
-        switch (w) {
-        case -1: return (a.gx0 - r.x) / r.dx;
-        case -2: return (a.gx1 - r.x) / r.dx;
-        case -3: return (a.gy0 - r.y) / r.dy;
-        case -4: return (a.gy1 - r.y) / r.dy;
-        case -5: return (a.gz0 - r.z) / r.dz;
-        default: return (a.gz1 - r.z) / r.dz;
-        }
-    }
-
-    // the reference's distance along the ray to the bisector plane of sites pr (the current cell) and pi
-    // (a neighbour), 0 when the ray moves away from it -- VoronoiMesh.cpp:790-806, same operation order
-    __device__ static __forceinline__ double planeDist(const Ray& r, double prx, double pry, double prz, double pix,
-                                                       double piy, double piz) {
-        const double nx = pix - prx, ny = piy - pry, nz = piz - prz;
-        const double ndotk = nx * r.dx + ny * r.dy + nz * r.dz;
-        if (!(ndotk > 0)) return 0;
-        const double px = 0.5 * (pix + prx), py = 0.5 * (piy + pry), pz = 0.5 * (piz + prz);
-        return (nx * (px - r.x) + ny * (py - r.y) + nz * (pz - r.z)) / ndotk;
-    }
-
-    __device__ static __forceinline__ void siteAt(const Args& a, int start, double& x, double& y, double& z) {
-        const double2 h0 = *reinterpret_cast<const double2*>(a.vorSlots + start);
-        const double2 h1 = *reinterpret_cast<const double2*>(a.vorSlots + start + 1);
-        x = h0.x; y = h0.y; z = h1.x;
-    }
-
-    // the operands of a step: the cell's header (exact site, density, id, neighbour count) and, for the
-    // bounds, the float offset D of the site from the ray's position and the direction in float
-    struct StepIn {
-        const VorEntry* B;
-        double pwx, pwy, pwz, rhow;
-        int idw, cnt;
-        float Dx, Dy, Dz, fkx, fky, fkz;
-        float eA, eA2, eB2;  // the cell's error terms: eA, 2 eA, 2 (eA |D|_1 + kVorEpsF max |n|^2)
-    };
-    // U: the least upper bound of the certain exits; L1 <= L2: the two least lower bounds of the possible
-    // exits, w1: the first one's `next`
-    struct Best {
-        float U, L1, L2;
-        int w1;
-    };
-
-    // the bounds [lo, hi] of one neighbour's plane distance, in single precision on coordinates scaled by
-    // a.vorScale (the entries' offsets are stored scaled): each float operation adds a few 2^-24 of the sum
-    // of absolute terms, which kVorEpsF covers with margin; an approximate reciprocal (1 ulp) is covered by
-    // the |s| term. Walls are stored as the bisector plane with the site's mirror image (the same plane),
-    // so every entry takes the same branch-free arithmetic; lo = hi = FLT_MAX: certainly no exit.
-    __device__ static __forceinline__ void bounds(const StepIn& s, const VorEntry& en, bool valid, float& lo,
-                                                  float& ucand) {
-        // the plane distance s = (n.D + |n|^2/2) / (n.k) = (m.D + 1/2) / (m.k) with m = n / |n|^2, the stored
-        // entry, and Cauchy-Schwarz error terms: |d(m.k)| <= eA and |d(m.D + 1/2)| <= eB = eA |D|_1 + kVorEpsF/2,
-        // at the cell's largest |m|_1 (vor_terms.hpp; several times the float roundings of the entries, D, k
-        // and the fused operations). 29 operations per entry (with n stored: 33; per-entry terms: 38; round
-        // 2's sums of the absolute terms of each product: 55); tools/vor_compact_check.cpp, mode r, checks
-        // the resulting steps against the reference's.
-        const float mx = en.ox, my = en.oy, mz = en.oz;  // m = n / |n|^2 (vor_terms.hpp)
-        const float den = fmaf(mz, s.fkz, fmaf(my, s.fky, mx * s.fkx));
-        const float num = fmaf(mz, s.Dz, fmaf(my, s.Dy, fmaf(mx, s.Dx, 0.5f)));
-        const float inv = __builtin_amdgcn_rcpf(den);
-        const float sa = num * inv;
-        const float err = fmaf(fmaf(fabsf(sa), s.eA2, s.eB2), inv, fabsf(sa) * kVorEpsF);
-        // den > 2 eA: the sign of n.k and the interval [sa - err, sa + err] are certain; den <= -eA: moving away for certain; otherwise (den = 0 included: m = 0 is a
-        // degenerate wall) the sign is uncertain: lo = -FLT_MAX. Entries past the count (`valid`), and the
-        // NaN padding after a cell's list (den NaN, so neither sure nor maybe): no exit. ucand: the upper
-        // bound of a certain exit (lo > 0), else FLT_MAX. Selected as floats, no bool temporaries.
-        const float lov = sa - err, hiv = sa + err;
-        const bool sure = valid && den > s.eA2;
-        const bool maybe = valid && den > -s.eA;
-        // (a sure interval wholly behind the ray, hiv <= 0, stays a possible exit, which the exact evaluation
-        // would drop: inside the cell no plane the ray moves towards lies behind it, so this happens at
-        // rounding level only -- tools/vor_compact_check.cpp, mode r: the same 297 exact re-evaluations in
-        // 1,004,001 steps with and without the check; C4 +0.7 %, profiles/r05_vor_behind_ab.txt)
-        lo = sure ? lov : (maybe ? -FLT_MAX : FLT_MAX);
-        ucand = (sure && lov > 0.f) ? hiv : FLT_MAX;
-    }
-
-    // one entry's bounds into the running Best, in list order
-    __device__ static __forceinline__ void take(Best& b, float lo, float ucand, int next) {
-        b.U = fminf(b.U, ucand);
-        b.w1 = lo < b.L1 ? next : b.w1;
-        b.L2 = __builtin_amdgcn_fmed3f(b.L1, b.L2, lo);
-        b.L1 = fminf(b.L1, lo);
-    }
-
-    // The start of a step: the cell's header h0..h2 (loaded with the first entries in the same round), the
-    // pending segment (r.ck = 1: the previous cell's segment, cell r.ci, density r.rho0, site r.bx0..bz0,
-    // ends on the bisector plane with this cell, whose exact site arrives with this load), and the bounds'
-    // operands. False: the ray ended.
-    template <class SegFn>
-    __device__ static __forceinline__ bool headFrom(const Args& a, Ray& r, StepIn& s, const double2& h0, const double2& h1,
-                                                    const int4& h2, SegFn seg) {
-        s.pwx = h0.x; s.pwy = h0.y; s.pwz = h1.x; s.rhow = h1.y;
-        s.idw = h2.x; s.cnt = h2.y;
-        const float eA = __int_as_float(h2.z), eBn = __int_as_float(h2.w);  // the cell's terms (upload)
-        if (r.ck) {
-            const double sq = planeDist(r, r.bx0, r.by0, r.bz0, s.pwx, s.pwy, s.pwz);
-            if (!seg(r.ci, r.rho0, sq)) return false;
-            r.x += (sq + a.eps) * r.dx; r.y += (sq + a.eps) * r.dy; r.z += (sq + a.eps) * r.dz;
-            r.ck = 0;
-        }
-        const float sc = a.vorScale;
-        s.Dx = (float)((s.pwx - r.x) * sc); s.Dy = (float)((s.pwy - r.y) * sc); s.Dz = (float)((s.pwz - r.z) * sc);
-        const float Dn = fabsf(s.Dx) + fabsf(s.Dy) + fabsf(s.Dz);  // |D|_1
-        s.fkx = (float)r.dx; s.fky = (float)r.dy; s.fkz = (float)r.dz;
-        s.eA = eA; s.eA2 = 2.0f * eA; s.eB2 = 2.0f * fmaf(eA, Dn, eBn);
-        return true;
-    }
-
-    // The end of a step, from the bounds over all entries: a single certain exit is taken (its exact
-    // distance follows from the next cell's header, r.ck = 1); otherwise the reference's rule, exactly,
-    // over the possible winners.
-    template <class SegFn>
-    __device__ static __forceinline__ bool decide(const Args& a, Ray& r, const StepIn& s, const Best& b, SegFn seg) {
-        const VorEntry* B = s.B;
-        const int cnt = s.cnt;
-        if (b.L1 != FLT_MAX && b.L2 > b.U) {
-            if (b.w1 >= 0) {  // the exit: its exact distance when the next cell's header arrives
-                r.ck = 1;
-                r.ci = s.idw; r.rho0 = s.rhow;
-                r.bx0 = s.pwx; r.by0 = s.pwy; r.bz0 = s.pwz;
-                r.cj = b.w1;
-                return true;
-            }
-            seg(s.idw, s.rhow, wallDist(a, r, b.w1));  // leaves the grid through a wall
-            return false;
-        }
-        // no exit, or several possible exits. An entry whose lower bound exceeds U lies beyond a certain
-        // exit, so it can neither win nor tie; a second pass over the (cached) entries collects the others
-        // in list order (the first of equal distances wins) and their sites arrive in one round trip. More
-        // than kVorCand of them: the whole list, in groups.
-        const double kx = r.dx, ky = r.dy, kz = r.dz;
-        constexpr int NO_INDEX = (int)0x80000000u;
-        double sq = kDblMax;
-        int mq = NO_INDEX;
-        auto consider = [&](int nxt, double pix, double piy, double piz) {
-            const double si = nxt < 0 ? wallDist(a, r, nxt) : planeDist(r, s.pwx, s.pwy, s.pwz, pix, piy, piz);
-            if (si > 0 && si < sq) { sq = si; mq = nxt; }
-        };
-        if (b.L1 != FLT_MAX) {
-            int c0 = 0, c1 = 0, c2 = 0, c3 = 0, nc = 0;
-            VorEntry e[kVorUnroll];
-            for (int q0 = 0; q0 < cnt; q0 += kVorUnroll) {
-                vorEntries(B, q0, e);
-#pragma unroll
-                for (int u = 0; u < kVorUnroll; u++) {
-                    float lo, uc;
-                    bounds(s, e[u], q0 + u < cnt, lo, uc);
-                    if (lo < FLT_MAX && lo <= b.U) {
-                        const int nx = e[u].next;
-                        c0 = nc == 0 ? nx : c0; c1 = nc == 1 ? nx : c1; c2 = nc == 2 ? nx : c2; c3 = nc == 3 ? nx : c3;
-                        nc++;
-                    }
-                }
-            }
-            if (nc <= kVorCand) {
-                const int cs[kVorCand] = {c0, c1, c2, c3};
-                double pix[kVorCand], piy[kVorCand], piz[kVorCand];
-#pragma unroll
-                for (int u = 0; u < kVorCand; u++) {
-                    pix[u] = piy[u] = piz[u] = 0.0;
-                    if (u < nc && cs[u] >= 0) siteAt(a, cs[u], pix[u], piy[u], piz[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < kVorCand; u++)
-                    if (u < nc) consider(cs[u], pix[u], piy[u], piz[u]);
-            } else {
-                constexpr int G = kVorFallbackGroup;
-                for (int q0 = 0; q0 < cnt; q0 += G) {
-                    int nxt[G];
-                    double pix[G], piy[G], piz[G];
-#pragma unroll
-                    for (int u = 0; u < G; u++) {
-                        nxt[u] = vorEntry(B, q0 + u).next;
-                        pix[u] = piy[u] = piz[u] = 0.0;
-                        if (q0 + u < cnt && nxt[u] >= 0) siteAt(a, nxt[u], pix[u], piy[u], piz[u]);
-                    }
-#pragma unroll
-                    for (int u = 0; u < G; u++)
-                        if (q0 + u < cnt) consider(nxt[u], pix[u], piy[u], piz[u]);
-                }
-            }
-        }
-        if (mq == NO_INDEX) {
-            // no exit found: advance by eps and locate again (VoronoiMesh.cpp:831-835)
-            r.x += kx * a.eps; r.y += ky * a.eps; r.z += kz * a.eps;
-            const int m = cellIndex(a, r.x, r.y, r.z);
-            if (m < 0) return false;
-            r.ci = m;
-            r.cj = a.vorStart[m];
-            return true;
-        }
-        if (!seg(s.idw, s.rhow, sq)) return false;
-        r.x += (sq + a.eps) * kx; r.y += (sq + a.eps) * ky; r.z += (sq + a.eps) * kz;
-        r.cj = mq;
-        return mq >= 0;
-    }
-
-    // One step (VoronoiMesh::path, VoronoiMesh.cpp:749-844), lane-serial over the cell's entries. r.cj:
-    // the block of the cell the ray is in. A step issues one round of loads (this cell's header and first
-    // entries) in the common case. It adds at most two segments (the pending one, and one more when the
-    // bounds leave several possible winners), see kSegsPerStep.
-    // the loads a step starts with: the cell's header and its first kVorGroups groups of entries (one round)
-    struct Load {
-        double2 h0, h1;
-        int4 h2;
-        VorEntry g[kVorGroups][kVorUnroll];
-    };
-    __device__ static __forceinline__ void stepLoad(const Args& a, const Ray& r, Load& L, bool act = true) {
-        // lanes without a ray load block 0: an unconditional load needs no merge of old and new register
-        // values (moves, which would wait for the loads right after their issue)
-        const VorEntry* B = a.vorSlots + (act ? r.cj : 0);
-        L.h0 = *reinterpret_cast<const double2*>(B);
-        L.h1 = *reinterpret_cast<const double2*>(B + 1);
-        L.h2 = *reinterpret_cast<const int4*>(B + 2);
-#pragma unroll
-        for (int gi = 0; gi < kVorGroups; gi++) vorEntries(B, gi * kVorUnroll, L.g[gi]);
-    }
-
-    template <class SegFn>
-    __device__ static __forceinline__ bool step(const Args& a, const Shared& sh, Ray& r, SegFn seg) {
-        Load L;
-        stepLoad(a, r, L);
-        return stepRest(a, sh, r, L, seg);
-    }
-
-    // the step from its loads (stepLoad): the trace kernel issues the Labs drain between the two, so the
-    // header's wait does not include the drain's atomics (vmcnt counts in issue order)
-    template <class SegFn>
-    __device__ static __forceinline__ bool stepRest(const Args& a, const Shared&, Ray& r, Load& L, SegFn seg) {
-        StepIn s;
-        s.B = a.vorSlots + r.cj;
-        Best b{FLT_MAX, FLT_MAX, FLT_MAX, 0};
-        // kVorGroups groups of entries in flight: they load with the header, and each group's next load is
-        // issued as soon as the group is consumed, so a cell with more than kVorUnroll neighbours does not
-        // wait for a second round trip
-        if (!headFrom(a, r, s, L.h0, L.h1, L.h2, seg)) return false;
-        // (the next groups are loaded only while the list lasts: loading them unconditionally -- past the list
-        // into the next block -- let the compiler drop the register moves at the join, but made C4 24 % slower,
-        // 9.53e7 -> 7.37e7 pkt/s, profiles/r04_ab_c4_vor_uncond_loads_c3c5_prefetch.txt; a lane past its list
-        // reading one line that all such lanes share instead: 208 -> 170 register moves, still 5 % slower,
-        // profiles/r05_vor_uncond_shared_ab.txt; round 0 peeled and round 1 loaded into registers of its
-        // own: 208 -> 146 moves, 245 VGPRs, C4 -0.4 %, the same file)
-        constexpr int NG = kVorGroups;
-        for (int q0 = 0; q0 < s.cnt; q0 += NG * kVorUnroll) {
-#pragma unroll
-            for (int gi = 0; gi < NG; gi++) {
-                const int qb = q0 + gi * kVorUnroll;
-                if (gi > 0 && qb >= s.cnt) break;
-#pragma unroll
-                for (int u = 0; u < kVorUnroll; u++) {
-                    float lo, uc;
-                    // (a cell's list is padded to whole groups with NaN entries: no count check per entry)
-                    bounds(s, L.g[gi][u], true, lo, uc);
-                    take(b, lo, uc, L.g[gi][u].next);
-                }
-                if (qb + NG * kVorUnroll < s.cnt) vorEntries(s.B, qb + NG * kVorUnroll, L.g[gi]);
-            }
-        }
-        return decide(a, r, s, b, seg);
-    }
-
-    __device__ static __forceinline__ int whichcell(const Args& a, const Shared&, double x, double y, double z) {
-        return cellIndex(a, x, y, z);
-    }
-
-    // VoronoiMesh::isPointClosestTo, over the exact sites of the cell's neighbours (their headers)
-    __device__ static __forceinline__ bool closestTo(const Args& a, double x, double y, double z, int m) {
-        auto d2 = [&](double sx, double sy, double sz) {
-            const double dx = x - sx, dy = y - sy, dz = z - sz;
-            return dx * dx + dy * dy + dz * dz;
-        };
-        const int start = a.vorStart[m];
-        double sx, sy, sz;
-        siteAt(a, start, sx, sy, sz);
-        const double target = d2(sx, sy, sz);
-        const int cnt = reinterpret_cast<const int4*>(a.vorSlots + start + 2)->y;
-        for (int q = 0; q < cnt; q++) {
-            const int nxt = vorEntry(a.vorSlots + start, q).next;
-            if (nxt < 0) continue;
-            siteAt(a, nxt, sx, sy, sz);
-            if (d2(sx, sy, sz) < target) return false;
-        }
-        return true;
-    }
-};
+// the grid walks: headers that compile only here, inside this namespace (as detect.hpp, emission.hpp and
+// density_sample.hpp below)
+#include "grid_cartesian.hpp"
+#include "grid_mesh2d.hpp"
+#include "grid_tree.hpp"
+#include "grid_voronoi.hpp"
 
 // ================================================================== trace kernel
 // GLOBAL: the Labs adds as global atomics (a table of 4 GiB or more, Args::labsGlobal), a kernel of its own:
@@ -1705,10 +641,6 @@ struct Tracer {
 
     __device__ __forceinline__ void drain() {
         static_assert(kLabsBuf >= 2 && kLabsBuf <= 64 && (kLabsBuf & (kLabsBuf - 1)) == 0, "kLabsBuf: power of 2");
-        constexpr int G = 64 / kLabsBuf;  // lanes per wave instruction
-        const int lane = threadIdx.x & 63;
-        const int wbase = threadIdx.x - lane;
-        const int j = lane & (kLabsBuf - 1);
 #pragma unroll
         for (int i = 0; i < kLabsBuf; i++) issue(i);
         npend = 0;
@@ -1937,50 +869,7 @@ struct Tracer {
     }
 };
 
-// Instrument::detect of one peel-off ray (FullInstrument.cpp:107-174 and the Simple/SED/Frame
-// variants): what it adds to instrument slot `slot` (FullInstrument: 0 transparent, 1 direct stellar,
-// 2 scattered stellar, 3 direct dust, 4 scattered dust, 5.. per scattering level); false if nothing.
-// Lextf = L e^{-tau}.
-__device__ __forceinline__ bool detectSlot(const DevInstr& ins, unsigned flags, int slot, double Lp, double Lextf,
-                                           double& v) {
-    v = Lextf;
-    if (ins.kind != SKIRT_INSTR_FULL) return slot == 0;
-    switch (rayCat(flags)) {
-    case CAT_STAR_DIRECT:
-        if (slot == 0) v = Lp;
-        return slot <= 1;
-    case CAT_STAR_SCATTERED: {
-        const int lev = rayLevel(flags);
-        return slot == 2 || (lev >= 1 && lev <= ins.levels && slot == 5 + lev - 1);
-    }
-    case CAT_DUST_DIRECT: return slot == 3;
-    default: return slot == 4;
-    }
-}
-
-// frame tally of an instrument: [lambda][pixel][slot] with the slots padded to slotStride (8 for a
-// FullInstrument with up to 3 scattering levels), so that one detection's adds fall in one 64-byte line
-__device__ __forceinline__ double* frameAt(const Args& a, const DevInstr& ins, int ell, int l, int slot) {
-    return a.tally + ins.frameBase + ((long long)ell * ins.nx * ins.ny + l) * ins.slotStride + slot;
-}
-
-// Instrument::detect of one peel-off ray with optical depth tau by one lane: SEDs into `sed` (LDS sums
-// of the workgroup) or, when null, the global tally; frames with f64 atomics
-__device__ __forceinline__ void detectPeel(const Args& a, const DevInstr& ins, unsigned flags, int l, double Lp,
-                                           double tau, double* sed) {
-    const double Lextf = Lp * exp(-tau);
-    const int nl = a.nlambda;
-    const int ell = rayEll(flags);
-    for (int slot = 0; slot < ins.nslots; slot++) {
-        double v;
-        if (!detectSlot(ins, flags, slot, Lp, Lextf, v)) continue;
-        if (ins.kind != SKIRT_INSTR_FRAME) {
-            if (sed) atomicAdd(&sed[ins.sedOff + slot * nl + ell], v);
-            else atomicAddF64(a.tally + ins.sedBase + slot * nl + ell, v);
-        }
-        if (l >= 0 && ins.kind != SKIRT_INSTR_SED) atomicAddF64(frameAt(a, ins, ell, l, slot), v);
-    }
-}
+#include "detect.hpp"
 
 // DustSystem::writeconvergence (DustSystem.cpp:195-250): the column density of the grid along a ray, as
 // DustGridPath::opticalDepth (DustGridPath.hpp:97-108) sums it with DustSystem::density (the cell's
@@ -2012,245 +901,7 @@ __global__ void __launch_bounds__(kBlock) columnKernel(const Args a, const doubl
     out[i] = tau;
 }
 
-// ================================================================== dust emission sources on the device
-// The grey-body emission spectrum of every cell and the per-wavelength cell distribution of the dust
-// phases (DustLib::calculate with AllCellsDustLib + GreyBodyDustEmissivity, DustLib.cpp:60-185,
-// GreyBodyDustEmissivity.cpp:19-43, DustMix::equilibrium DustMix.cpp:689-712; cell luminosities and
-// NR::cdf of PanMonteCarloSimulation.cpp:193-205, 273-294), computed from the device tallies so the
-// self-absorption cycles never leave the GPU. Reference cell order, like the host restatement
-// (host/dustemission.cpp), which the tests compare against.
-struct EmisArgs {
-    int ncells, nlambda, ncomp, ntemp;
-    const int* devCell;          // reference cell -> device cell (null: identity)
-    const double* labs;          // [nlambda][device cell]
-    const double* labsDust;      // same, or null
-    const double* rho;           // [device cell][ncomp]
-    const double* volume;        // [reference cell]
-    const double* kabs;          // [ncomp][nlambda]
-    const double* sigmaabs;      // [ncomp][nlambda]
-    const double* mu;            // [ncomp]
-    const double* Tv;            // [ntemp]
-    const double* planckabs;     // [ncomp][ntemp]
-    const double* lambda;        // [nlambda]
-    const double* dlambda;       // [nlambda]
-    int labsStride;              // Labs row length
-    double* lv;                  // out [nlambda][ncells]
-    double* cdf;                 // out [nlambda][ncells + 1]
-    double* ltot;                // out [nlambda]
-    double* blockSums;           // scratch [nlambda][nblocks]
-    int nblocks;
-};
-
-__device__ __forceinline__ double planckB(double T, double lambda) {  // PlanckFunction
-    const double h = 6.62606957e-34, c = 2.99792458e8, k = 1.3806488e-23;
-    const double x = h * c / (lambda * k * T);
-    return 2.0 * h * c * c / pow(lambda, 5) / (exp(x) - 1.0);
-}
-
-__global__ void __launch_bounds__(kBlock) cellSpectraKernel(const EmisArgs e) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= e.ncells) return;
-    const int Nl = e.nlambda;
-    const size_t S = e.labsStride;
-    const int dm = e.devCell ? e.devCell[m] : m;
-    // PanDustSystem::Labs(m): stellar sum, continued by the dust sum
-    double Labsbol = 0;
-    for (int ell = 0; ell < Nl; ell++) Labsbol += e.labs[ell * S + dm];
-    if (e.labsDust)
-        for (int ell = 0; ell < Nl; ell++) Labsbol += e.labsDust[ell * S + dm];
-    // J_lambda is needed only for the absorbed power of each component, and the emission spectrum Lv is
-    // accumulated in the cell's own column of the output (the arithmetic of the host restatement, one
-    // operation at a time), so any number of wavelengths fits
-    const double fac = 4.0 * M_PI * e.volume[m];
-    auto meanIntensity = [&](int ell) {  // DustSystem::meanintensityv
-        double L = 0;
-        L += e.labs[ell * S + dm];
-        if (e.labsDust) L += e.labsDust[ell * S + dm];
-        double kr = 0.0;
-        for (int h = 0; h < e.ncomp; h++) kr += e.kabs[h * Nl + ell] * e.rho[(size_t)dm * e.ncomp + h];
-        const double J = L / (kr * fac) / e.dlambda[ell];
-        return isfinite(J) ? J : 0.0;
-    };
-    double* Lv = e.lv + m;  // Lv[ell] at Lv[ell * ncells]
-    const size_t N = e.ncells;
-    for (int ell = 0; ell < Nl; ell++) Lv[ell * N] = 0.0;
-    for (int h = 0; h < e.ncomp; h++) {
-        // DustMix::equilibrium -> invplanckabs (NR::locate_clip + linear interpolation)
-        const double* sa = e.sigmaabs + h * Nl;
-        double pa = 0.0;
-        for (int ell = 0; ell < Nl; ell++) pa += sa[ell] * meanIntensity(ell) * e.dlambda[ell];
-        const double* tab = e.planckabs + (size_t)h * e.ntemp;
-        int p;
-        if (pa < tab[0]) p = 0;
-        else {
-            int jl = -1, ju = e.ntemp - 1;
-            while (ju - jl > 1) { const int jm = (ju + jl) >> 1; if (pa < tab[jm]) ju = jm; else jl = jm; }
-            p = jl;
-        }
-        const double T = e.Tv[p] + ((pa - tab[p]) / (tab[p + 1] - tab[p])) * (e.Tv[p + 1] - e.Tv[p]);
-        const double w = e.ncomp > 1 ? e.rho[(size_t)dm * e.ncomp + h] : 1.0;
-        for (int ell = 0; ell < Nl; ell++) {
-            double ev = 0.0;
-            ev += sa[ell] * planckB(T, e.lambda[ell]);
-            ev /= e.mu[h];
-            if (e.ncomp > 1) Lv[ell * N] += ev * w;
-            else Lv[ell * N] = ev;
-        }
-    }
-    double total = 0.0;
-    for (int ell = 0; ell < Nl; ell++) {
-        const double v = Lv[ell * N] * e.dlambda[ell];
-        Lv[ell * N] = v;
-        total += v;
-    }
-    for (int ell = 0; ell < Nl; ell++) {
-        const double lum = total > 0 ? Lv[ell * N] / total : Lv[ell * N];
-        Lv[ell * N] = Labsbol > 0.0 ? Labsbol * lum : 0.0;
-    }
-}
-
-// per wavelength: sums of kBlock consecutive cells
-__global__ void __launch_bounds__(kBlock) cellBlockSumKernel(const EmisArgs e) {
-    __shared__ double red[kBlock];
-    const int ell = blockIdx.y, b = blockIdx.x, m = b * kBlock + threadIdx.x;
-    red[threadIdx.x] = m < e.ncells ? e.lv[(size_t)ell * e.ncells + m] : 0.0;
-    __syncthreads();
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) e.blockSums[(size_t)ell * e.nblocks + b] = red[0];
-}
-
-// per wavelength (one block each): exclusive scan of the block sums and the total. Each thread sums a
-// contiguous chunk of the block sums, the chunk sums are scanned in LDS, and each thread then writes its
-// chunk's exclusive prefixes (a single thread walking all block sums took 3 ms per call on C5).
-__global__ void __launch_bounds__(kBlock) cellScanBlocksKernel(const EmisArgs e) {
-    __shared__ double part[kBlock];
-    const int ell = blockIdx.x;
-    double* bs = e.blockSums + (size_t)ell * e.nblocks;
-    const int per = (e.nblocks + kBlock - 1) / kBlock;
-    const int b0 = min(e.nblocks, (int)threadIdx.x * per), b1 = min(e.nblocks, b0 + per);
-    double sum = 0;
-    for (int b = b0; b < b1; b++) sum += bs[b];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {  // inclusive Hillis-Steele scan of the chunk sums
-        const double v = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0.0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    double run = threadIdx.x ? part[threadIdx.x - 1] : 0.0;
-    for (int b = b0; b < b1; b++) {
-        const double v = bs[b];
-        bs[b] = run;
-        run += v;
-    }
-    if (threadIdx.x == kBlock - 1) e.ltot[ell] = part[kBlock - 1];
-}
-
-// the normalized cumulative distribution: X[0] = 0, X[m+1] = (sum of Lv[0..m]) / Ltot
-__global__ void __launch_bounds__(kBlock) cellCdfKernel(const EmisArgs e) {
-    __shared__ double sc[kBlock];
-    const int ell = blockIdx.y, b = blockIdx.x, m = b * kBlock + threadIdx.x;
-    const int N = e.ncells;
-    sc[threadIdx.x] = m < N ? e.lv[(size_t)ell * N + m] : 0.0;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {  // inclusive Hillis-Steele scan
-        const double v = threadIdx.x >= off ? sc[threadIdx.x - off] : 0.0;
-        __syncthreads();
-        sc[threadIdx.x] += v;
-        __syncthreads();
-    }
-    const double total = e.ltot[ell];
-    double* X = e.cdf + (size_t)ell * (N + 1);
-    if (m < N) X[m + 1] = total > 0 ? (e.blockSums[(size_t)ell * e.nblocks + b] + sc[threadIdx.x]) / total : 0.0;
-    if (m == 0) X[0] = 0.0;
-}
-
-// NR::locate_clip over a table in global memory (n entries): the largest j <= n - 2 with v[j] <= q, 0 below v[0]
-__device__ __forceinline__ int locateClipTable(const double* v, int n, double q) {
-    if (q < v[0]) return 0;
-    int jl = -1, ju = n - 1;
-    while (ju - jl > 1) {
-        const int jm = (ju + jl) >> 1;
-        if (q < v[jm]) ju = jm;
-        else jl = jm;
-    }
-    return jl;
-}
-
-// A guide table over a CDF of N + 1 entries: G[k] = locate_clip(v, k / N), k = 0 .. N. A draw q then only
-// bisects [G[k], G[k + 1]] with k = floor(q N) -- two or three dependent loads instead of log2(N) ~ 20 (the
-// dust-phase launch draws a cell from 622,490 per packet in C5).
-__global__ void __launch_bounds__(kBlock) cellGuideKernel(const double* cdf, int* guide, int N) {
-    const int ell = blockIdx.y, k = blockIdx.x * kBlock + threadIdx.x;
-    if (k > N) return;
-    const double* v = cdf + (size_t)ell * (N + 1);
-    guide[(size_t)ell * (N + 1) + k] = locateClipTable(v, N + 1, (double)k / (double)N);
-}
-
-// locate_clip(v, N + 1, q) through the guide table: the bracket [G[k], G[k + 1] + 1) holds the answer when
-// v[G[k]] <= q and q < v[G[k + 1] + 1] (or the bracket ends at the table's last index) -- checked, since
-// floor(q N) may round across a bucket edge; otherwise the whole table is bisected. Within a valid bracket
-// the bisection finds the same largest j with v[j] <= q as the full one.
-__device__ __forceinline__ int locateGuided(const double* v, const int* G, int N, double q) {
-    const int k = max(0, min(N - 1, static_cast<int>(q * (double)N)));
-    const int lo = G[k], hi = G[k + 1] + 1;
-    if (!(v[lo] <= q) || (hi < N && !(q < v[hi]))) return locateClipTable(v, N + 1, q);
-    int jl = lo, ju = hi;
-    while (ju - jl > 1) {
-        const int jm = (ju + jl) >> 1;
-        if (q < v[jm]) ju = jm;
-        else jl = jm;
-    }
-    return jl;
-}
-
-// fills the leaf map: one thread per finest-level cell descends the (checked) tree by its index bits
-// (a k-d tree by the bit of its split axis at that axis' depth)
-__global__ void __launch_bounds__(kBlock) buildLeafMapKernel(LeafEntry* map, const int* firstChild, const signed char* splitDir,
-                                                             const int* cellnumber, const double* rho, int ncomp, int L) {
-    const int N = 1 << L;
-    const unsigned long long n = leafMapSize(N);
-    for (unsigned long long q = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; q < n;
-         q += (unsigned long long)gridDim.x * blockDim.x) {
-        unsigned fx = 0, fy = 0, fz = 0;
-        {  // inverse of leafIndex
-            const unsigned long long nb = leafBricks(N), br = q >> 3;
-            fx = (unsigned)(2 * (br / (nb * nb)) + ((q >> 2) & 1u));
-            fy = (unsigned)(2 * ((br / nb) % nb) + ((q >> 1) & 1u));
-            fz = (unsigned)(2 * (br % nb) + (q & 1u));
-            fx = min(fx, (unsigned)N - 1u); fy = min(fy, (unsigned)N - 1u); fz = min(fz, (unsigned)N - 1u);
-        }
-        int node = 0, level = 0;
-        LeafEntry e;
-        if (splitDir) {
-            int lv[3] = {0, 0, 0};
-            const unsigned f[3] = {fx, fy, fz};
-            while (firstChild[node] >= 0) {
-                const int d = splitDir[node];
-                const int bit = L - 1 - lv[d];
-                lv[d]++;
-                node = firstChild[node] + (int)((f[d] >> bit) & 1u);
-            }
-            e.cl = (unsigned)cellnumber[node] |
-                   ((unsigned)(L - lv[0]) | (unsigned)(L - lv[1]) << 3 | (unsigned)(L - lv[2]) << 6) << kBinCellBits;
-        } else {
-            while (firstChild[node] >= 0) {
-                const int bit = L - 1 - level;
-                node = firstChild[node] + (int)((fx >> bit) & 1u) + 2 * (int)((fy >> bit) & 1u) + 4 * (int)((fz >> bit) & 1u);
-                level++;
-            }
-            e.cl = (unsigned)cellnumber[node] | ((unsigned)level << kLeafLevelShift);
-        }
-        const int cell = cellnumber[node];
-        e.node = node;
-        e.rho0 = rho[(size_t)cell * ncomp];
-        map[q] = e;
-    }
-}
+#include "emission.hpp"
 
 // CONT: continuous scattering (the FILL rays record their dust segments); its own instantiations keep
 // the recording out of the other kernels' registers
@@ -2261,19 +912,19 @@ __device__ __forceinline__ void traceBody(const Args& a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         // reset the counters the next event iteration appends to (nobody else uses them now)
-        CTR(a.ctr, 1 - a.parity) = 0;  // ray count of the next iteration
-        CTR(a.ctr, 2 + a.parity) = 0;  // active list just consumed by the event kernel
-        CTR(a.ctr, 8 + (1 - a.parity)) = 0;  // the next iteration's WALK rays
+        CTR(a.ctr, CTR_RAYS + (1 - a.parity)) = 0;  // the next iteration's
+        CTR(a.ctr, CTR_ACTIVE + a.parity) = 0;  // just consumed by the event kernel
+        CTR(a.ctr, CTR_WALK + (1 - a.parity)) = 0;  // the next iteration's
     }
-    // the iteration's rays: ctr[q] from the bottom of the queue, then the WALK rays ctr[8 + q] from its top
+    // the iteration's rays: CTR_RAYS from the bottom of the queue, then the CTR_WALK rays from its top
     // (Args::walkBack), pulled last: the short WALK paths fill the lanes that the long FILL and peel-off
     // paths free at the end of a launch, instead of idling until the launch's longest path ends
-    const unsigned int nfront = CTR(a.ctr, a.parity);
-    if (nfront + CTR(a.ctr, 8 + a.parity) == 0) return;  // an iteration after the end of the phase
+    const unsigned int nfront = CTR(a.ctr, CTR_RAYS + a.parity);
+    if (nfront + CTR(a.ctr, CTR_WALK + a.parity) == 0) return;  // an iteration after the end of the phase
     // the front rays (growing up from 0) and the WALK rays (growing down from rayCap - 1) must not meet:
     // the event and continuous peel-off kernels reserved them independently, so this is the first point
     // where both totals are final; an overflow fails the phase instead of tracing overwritten records
-    if ((unsigned long long)nfront + CTR(a.ctr, 8 + a.parity) > (unsigned long long)a.rayCap) {
+    if ((unsigned long long)nfront + CTR(a.ctr, CTR_WALK + a.parity) > (unsigned long long)a.rayCap) {
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.error, ERR_QUEUE);
         return;
     }
@@ -2292,7 +943,7 @@ __device__ __forceinline__ void traceBody(const Args& a) {
     if (threadIdx.x < 3 * (kBlock / 64)) T.waveSegs[threadIdx.x] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const unsigned int nrays = nfront + CTR(a.ctr, 8 + a.parity);
+    const unsigned int nrays = nfront + CTR(a.ctr, CTR_WALK + a.parity);
     Ray r;
     r.mode = RAY_NONE;
     r.id = 0;
@@ -2306,7 +957,7 @@ __device__ __forceinline__ void traceBody(const Args& a) {
     bool haveNext = false;
     auto reserve = [&]() {
         unsigned int base = 0;
-        if (lane == 0) base = atomicAdd(CTRP(a.ctr, 4), kPullChunk);
+        if (lane == 0) base = atomicAdd(CTRP(a.ctr, CTR_PULL), kPullChunk);
         return __shfl(base, 0);
     };
     while (true) {
@@ -2350,12 +1001,9 @@ __device__ __forceinline__ void traceBody(const Args& a) {
             if constexpr (!STORE) {
             } else if constexpr (kSegsPerStep<GRID> == 1) {
                 T.drainStep();  // one drain instruction per step
-            } else if (SKIRT_VOR_DRAIN2) {
+            } else {
                 static_assert(kSegsPerStep<GRID> == 2, "two drains per step hold two adds per step");
                 T.drainStep2();
-            } else {
-                // a buffer without room for another step's adds: issue the wave's adds
-                if (__ballot(T.npend > kLabsBuf - kSegsPerStep<GRID>)) T.drain();
             }
         }
     }
@@ -2384,59 +1032,6 @@ __global__ void __launch_bounds__(kBlock) SKIRT_NOSTORE_TRACE_ATTR traceKernelNo
 template <bool ONECOMP, bool CONT, bool GLOBAL = false>
 __global__ void __launch_bounds__(kBlock) SKIRT_VOR_TRACE_ATTR traceKernelVor(const Args a) {
     traceBody<SKIRT_GRID_VORONOI, ONECOMP, CONT, true, GLOBAL>(a);
-}
-
-// the detections of this iteration's peel-off rays (their optical depths are in the queue now)
-__global__ void __launch_bounds__(kBlock) detectKernel(const Args a) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const unsigned int nrays = CTR(a.ctr, 5 + a.parity);  // this iteration's detection records
-    if (nrays == 0) return;
-    Shared sh = stageTables(a, lds, STAGE_INSTR);
-    const int copies = a.detCopies;
-    for (int q = threadIdx.x; q < copies * a.nsed; q += blockDim.x) sh.sed[q] = 0.0;
-    __syncthreads();
-    unsigned int detects = 0;
-    // eight lanes per ray, one per instrument slot (mod 8): the frame adds of one detection fall in one
-    // 64-byte line (frameAt) and leave in one wave instruction, so they share one atomic request. Each
-    // group of 8 lanes sums SEDs into its own LDS copy (up to 8 copies, as many as the LDS holds): the 8
-    // rays of an instruction mostly hit the same few (slot, wavelength) sums, which one copy would
-    // serialize. Without room for one copy (very many wavelengths x slots) the SED adds go to the tally.
-    const int lane = threadIdx.x & 63, sub = lane & 7;
-    double* sed = copies ? sh.sed + ((lane >> 3) & (copies - 1)) * a.nsed : nullptr;
-    const unsigned int waves = gridDim.x * (blockDim.x / 64);
-    const unsigned int wave = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
-    for (unsigned int base = wave * 8; base < nrays; base += waves * 8) {
-        const unsigned int id = base + (lane >> 3);
-        if (id >= nrays) continue;
-        const DetRec d = a.det[id];
-        const unsigned flags = d.flags;
-        const DevInstr& ins = sh.instr[rayInstr(flags)];
-        const int l = d.l, ell = rayEll(flags);
-        const double Lp = d.Lp, Lextf = Lp * exp(-d.tau);
-        for (int slot = sub; slot < ins.nslots; slot += 8) {
-            double v;
-            if (!detectSlot(ins, flags, slot, Lp, Lextf, v)) continue;
-            if (ins.kind != SKIRT_INSTR_FRAME) {
-                if (sed) atomicAdd(&sed[ins.sedOff + slot * a.nlambda + ell], v);
-                else atomicAddF64(a.tally + ins.sedBase + slot * a.nlambda + ell, v);
-            }
-            if (l >= 0 && ins.kind != SKIRT_INSTR_SED) atomicAddF64(frameAt(a, ins, ell, l, slot), v);
-        }
-        if (sub == 0) detects++;
-    }
-    // flush the per-workgroup SED sums
-    __syncthreads();
-    for (int q = threadIdx.x; copies && q < a.nsed; q += blockDim.x) {
-        double v = 0.0;
-        for (int g = 0; g < copies; g++) v += sh.sed[g * a.nsed + q];
-        if (v != 0.0) {
-            int ii = 0;
-            while (ii + 1 < a.ninstr && sh.instr[ii + 1].sedOff <= q) ii++;
-            atomicAddF64(a.tally + sh.instr[ii].sedBase + (q - sh.instr[ii].sedOff), v);
-        }
-    }
-    const unsigned long long vals[8] = {0, 0, 0, 0, detects, 0, 0, 0};
-    flushStats(a, vals);
 }
 
 // ================================================================== event kernel
@@ -2896,112 +1491,50 @@ struct Events {
 // peel-off set queued by a slot in this iteration
 enum PeelKind : int { PEEL_NONE = 0, PEEL_EMISSION = 1, PEEL_SCATTER = 2 };
 
-// Block-wide reservation on shared counters: every thread of the block calls it with its counts c0, c1
-// (either may be 0); one atomic per counter per block (a device-wide counter serializes its
-// atomics, so one per block instead of one per wave) returns each thread's first index in r0, r1.
-// wave totals and the block's bases go through `scratch` (static LDS, 2 * (kBlock / 64) + 2 words).
-template <class T0, class T1>
-__device__ __forceinline__ void blockReserve(T0* ctr0, T0 c0, T0& r0, T1* ctr1, T1 c1, T1& r1, unsigned long long* scratch) {
+// Block-wide reservation on N shared counters of one type: every thread of the block calls it with its counts
+// c (any may be 0); one atomic per counter per block (a device-wide counter serializes its atomics, so one per
+// block instead of one per wave), issued by the first lane of wave q for counter q, returns each thread's
+// first index in r. Wave totals and the block's bases go through `scratch` (static LDS,
+// N * (kBlock / 64) + N words).
+template <class T, int N>
+__device__ __forceinline__ void blockReserve(T* const (&ctr)[N], const T (&c)[N], T (&r)[N], unsigned long long* scratch) {
+    static_assert(kBlock >= 64 * N, "blockReserve needs one wave per counter");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int W = kBlock / 64;
-    T0 i0 = c0;
-    T1 i1 = c1;
+    T in[N];
+#pragma unroll
+    for (int q = 0; q < N; q++) in[q] = c[q];
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        const T0 v0 = __shfl_up(i0, off);
-        const T1 v1 = __shfl_up(i1, off);
-        if (lane >= off) { i0 += v0; i1 += v1; }
-    }
-    if (lane == 63) { scratch[wave] = (unsigned long long)i0; scratch[W + wave] = (unsigned long long)i1; }
-    __syncthreads();
-    T0 w0 = 0, t0 = 0;
-    T1 w1 = 0, t1 = 0;
+        T v[N];
 #pragma unroll
-    for (int w = 0; w < W; w++) {
-        const T0 s0 = (T0)scratch[w];
-        const T1 s1 = (T1)scratch[W + w];
-        if (w < wave) { w0 += s0; w1 += s1; }
-        t0 += s0; t1 += s1;
-    }
-    if (threadIdx.x == 0) scratch[2 * W] = (ctr0 && t0) ? (unsigned long long)atomicAdd(ctr0, t0) : 0ull;
-    if (threadIdx.x == 64) scratch[2 * W + 1] = (ctr1 && t1) ? (unsigned long long)atomicAdd(ctr1, t1) : 0ull;
-    __syncthreads();
-    r0 = (T0)scratch[2 * W] + w0 + i0 - c0;
-    r1 = (T1)scratch[2 * W + 1] + w1 + i1 - c1;
-    __syncthreads();  // the scratch words are reused by the next call
-}
-
-// three counters at once (scratch: 3 * (kBlock / 64) + 3 words)
-__device__ __forceinline__ void blockReserve3(unsigned* ctr0, unsigned c0, unsigned& r0, unsigned* ctr1, unsigned c1,
-                                              unsigned& r1, unsigned* ctr2, unsigned c2, unsigned& r2,
-                                              unsigned long long* scratch) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int W = kBlock / 64;
-    unsigned i0 = c0, i1 = c1, i2 = c2;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned v0 = __shfl_up(i0, off), v1 = __shfl_up(i1, off), v2 = __shfl_up(i2, off);
-        if (lane >= off) { i0 += v0; i1 += v1; i2 += v2; }
-    }
-    if (lane == 63) { scratch[wave] = i0; scratch[W + wave] = i1; scratch[2 * W + wave] = i2; }
-    __syncthreads();
-    unsigned w0 = 0, w1 = 0, w2 = 0, t0 = 0, t1 = 0, t2 = 0;
-#pragma unroll
-    for (int w = 0; w < W; w++) {
-        const unsigned s0 = (unsigned)scratch[w], s1 = (unsigned)scratch[W + w], s2 = (unsigned)scratch[2 * W + w];
-        if (w < wave) { w0 += s0; w1 += s1; w2 += s2; }
-        t0 += s0; t1 += s1; t2 += s2;
-    }
-    if (threadIdx.x == 0) scratch[3 * W] = t0 ? atomicAdd(ctr0, t0) : 0u;
-    if (threadIdx.x == 64) scratch[3 * W + 1] = t1 ? atomicAdd(ctr1, t1) : 0u;
-    if (threadIdx.x == 128) scratch[3 * W + 2] = t2 ? atomicAdd(ctr2, t2) : 0u;
-    __syncthreads();
-    r0 = (unsigned)scratch[3 * W] + w0 + i0 - c0;
-    r1 = (unsigned)scratch[3 * W + 1] + w1 + i1 - c1;
-    r2 = (unsigned)scratch[3 * W + 2] + w2 + i2 - c2;
-    __syncthreads();  // the scratch words are reused by the next call
-}
-
-// four counters at once (scratch: 4 * (kBlock / 64) + 4 words); the first lane of wave q issues counter q's atomic
-static_assert(kBlock >= 256, "blockReserve4 needs four waves per block");
-__device__ __forceinline__ void blockReserve4(unsigned* const (&ctr)[4], const unsigned (&c)[4], unsigned (&r)[4],
-                                              unsigned long long* scratch) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int W = kBlock / 64;
-    unsigned in[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) in[q] = c[q];
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        unsigned v[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = __shfl_up(in[q], off);
+        for (int q = 0; q < N; q++) v[q] = __shfl_up(in[q], off);
         if (lane >= off) {
 #pragma unroll
-            for (int q = 0; q < 4; q++) in[q] += v[q];
+            for (int q = 0; q < N; q++) in[q] += v[q];
         }
     }
     if (lane == 63) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) scratch[q * W + wave] = in[q];
+        for (int q = 0; q < N; q++) scratch[q * W + wave] = in[q];
     }
     __syncthreads();
-    unsigned w[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
+    T w[N] = {}, t[N] = {};
 #pragma unroll
     for (int ww = 0; ww < W; ww++) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const unsigned sv = (unsigned)scratch[q * W + ww];
+        for (int q = 0; q < N; q++) {
+            const T sv = (T)scratch[q * W + ww];
             if (ww < wave) w[q] += sv;
             t[q] += sv;
         }
     }
 #pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (threadIdx.x == 64 * q) scratch[4 * W + q] = t[q] ? atomicAdd(ctr[q], t[q]) : 0u;
+    for (int q = 0; q < N; q++)
+        if (threadIdx.x == 64 * q) scratch[N * W + q] = t[q] ? atomicAdd(ctr[q], t[q]) : T(0);
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < 4; q++) r[q] = (unsigned)scratch[4 * W + q] + w[q] + in[q] - c[q];
+    for (int q = 0; q < N; q++) r[q] = (T)scratch[N * W + q] + w[q] + in[q] - c[q];
     __syncthreads();  // the scratch words are reused by the next call
 }
 
@@ -3019,13 +1552,13 @@ template <int GRID, bool ONECOMP>
 __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Args a) {
     __shared__ unsigned long long resv[4 * (kBlock / 64) + 4];
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    if (blockIdx.x == 0 && threadIdx.x == 0) CTR(a.ctr, 4) = 0;  // the trace kernel's pull counter
-    if (!a.init && CTR(a.ctr, 2 + a.parity) == 0) return;  // an iteration after the end of the phase
+    if (blockIdx.x == 0 && threadIdx.x == 0) CTR(a.ctr, CTR_PULL) = 0;
+    if (!a.init && CTR(a.ctr, CTR_ACTIVE + a.parity) == 0) return;  // an iteration after the end of the phase
     Shared sh = stageTables(a, lds, gridParts<GRID>() | STAGE_OPTICS | STAGE_INSTR);
     Events<GRID, ONECOMP> E{a, sh};
     const int lane = threadIdx.x & 63;
     const unsigned long long total = a.end - a.first;
-    const unsigned int nwork = a.init ? (unsigned)a.nslots : CTR(a.ctr, 2 + a.parity);
+    const unsigned int nwork = a.init ? (unsigned)a.nslots : CTR(a.ctr, CTR_ACTIVE + a.parity);
     const int* actIn = a.act[a.parity];
     int* actOut = a.act[1 - a.parity];
     const unsigned int stride = gridDim.x * blockDim.x;
@@ -3107,9 +1640,11 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
         // slots without a packet claim the next global packet indices (one atomic per block)
         bool need = valid && p.state == S_NEW && mainMode == RAY_NONE;
         while (__syncthreads_or(need)) {
-            unsigned long long idx = 0;
-            unsigned int unused = 0;
-            blockReserve<unsigned long long, unsigned int>(a.claim, need ? 1ull : 0ull, idx, nullptr, 0u, unused, resv);
+            unsigned long long* const ctrs[1] = {a.claim};
+            const unsigned long long cnt[1] = {need ? 1ull : 0ull};
+            unsigned long long res[1];
+            blockReserve(ctrs, cnt, res, resv);
+            const unsigned long long idx = res[0];
             if (need) {
                 if (idx >= total) need = false;  // exhausted: the slot retires
                 else if (E.launch(p, globalPacket(a, a.first + idx))) {
@@ -3155,11 +1690,11 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
         const bool back = a.walkBack && mainMode == RAY_WALK;
         unsigned int pos, apos, dpos, wpos;
         {
-            unsigned* const ctrs[4] = {CTRP(a.ctr, a.parity), CTRP(a.ctr, 2 + (1 - a.parity)), CTRP(a.ctr, 5 + a.parity),
-                                       CTRP(a.ctr, 8 + a.parity)};
+            unsigned* const ctrs[4] = {CTRP(a.ctr, CTR_RAYS + a.parity), CTRP(a.ctr, CTR_ACTIVE + (1 - a.parity)),
+                                       CTRP(a.ctr, CTR_DET + a.parity), CTRP(a.ctr, CTR_WALK + a.parity)};
             const unsigned cnt[4] = {(unsigned)nray - (back ? 1u : 0u), active ? 1u : 0u, (unsigned)npeel, back ? 1u : 0u};
             unsigned res[4];
-            blockReserve4(ctrs, cnt, res, resv);
+            blockReserve(ctrs, cnt, res, resv);
             pos = res[0]; apos = res[1]; dpos = res[2]; wpos = res[3];
         }
         // the queue holds rayCap records (ensurePool sizes it for the slots' most rays per iteration): a
@@ -3255,9 +1790,9 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
 // outside its field), one writes them into the space reserved for the block.
 template <int GRID, bool ONECOMP>
 __global__ void __launch_bounds__(kBlock) contKernel(const Args a) {
-    __shared__ unsigned long long resv[3 * (kBlock / 64) + 3];
+    __shared__ unsigned long long resv[2 * (kBlock / 64) + 2];
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    const unsigned int nwork = CTR(a.ctr, 2 + a.parity);
+    const unsigned int nwork = CTR(a.ctr, CTR_ACTIVE + a.parity);
     if (nwork == 0) return;
     Shared sh = stageTables(a, lds, gridParts<GRID>() | STAGE_OPTICS | STAGE_INSTR);
     Events<GRID, ONECOMP> E{a, sh};
@@ -3300,9 +1835,12 @@ __global__ void __launch_bounds__(kBlock) contKernel(const Args a) {
             for (int i = 0; i < a.ninstr; i++)
                 if (!(sh.instr[i].kind == SKIRT_INSTR_FRAME && E.pixel(sh.instr[i], q) < 0)) nray++;
         }
-        unsigned int pos = 0, dpos = 0, unused = 0;
-        blockReserve3(CTRP(a.ctr, a.parity), nray, pos, CTRP(a.ctr, 7), 0u, unused, CTRP(a.ctr, 5 + a.parity), nray, dpos,
-                      resv);
+        // a ray and a detection record per peel-off
+        unsigned* const ctrs[2] = {CTRP(a.ctr, CTR_RAYS + a.parity), CTRP(a.ctr, CTR_DET + a.parity)};
+        const unsigned cnt[2] = {nray, nray};
+        unsigned res[2];
+        blockReserve(ctrs, cnt, res, resv);
+        unsigned int pos = res[0], dpos = res[1];
         // (the WALK rays of the event kernel that follows are reserved from the queue's top later: the trace
         // kernel checks that the two regions do not meet)
         if (nray && (pos + nray > (unsigned)a.rayCap || dpos + nray > (unsigned)(a.rayCap - a.nslots))) {
@@ -3585,17 +2123,55 @@ const void* traceKernelOf(int kind, bool one, bool continuous, bool global, bool
 // slot pool: the ray queue, SoA packet state, per-slot results and two active lists of nslots slots
 // With continuous scattering every slot may also queue one peel-off per instrument and recorded path
 // segment in one iteration, and keeps the dust segments of its last path (kPathCap each).
+//
+// The pool's layout, written once: poolLayout hands out the arrays from `base` in this order and returns the
+// bytes they take; with a null base it only counts them (ensurePool). The records of 16-byte alignment come
+// first, from the allocation's start, each a whole number of 16-byte chunks; then the arrays of doubles, then
+// the 4-byte ones. The path records are aligned again: that padding comes out of the kPoolSpare bytes.
+static_assert(sizeof(RayRec) % 16 == 0 && alignof(RayRec) == 16 && sizeof(DetRec) % 16 == 0 && alignof(DetRec) == 16 &&
+                  alignof(PathRec) <= 16,
+              "pool order: ray records, detection records, 8-byte arrays, 4-byte arrays, aligned path records");
+constexpr size_t kPoolSpare = 4096;
+size_t poolLayout(char* base, size_t nslots, size_t rayCap, bool detPair, bool path, Args& a) {
+    char* p = base;
+    size_t bytes = 0;
+    auto take = [&](auto*& d, size_t count) {
+        using T = std::remove_reference_t<decltype(*d)>;
+        d = reinterpret_cast<T*>(p);
+        if (base) p += count * sizeof(T);
+        bytes += count * sizeof(T);
+    };
+    take(a.rays, rayCap);
+    // at most one peel-off per instrument and slot per iteration, in one region or one per iteration parity
+    take(a.det, (detPair ? 2 : 1) * (rayCap - nslots));
+    for (double** d : {&a.srx, &a.sry, &a.srz, &a.skx, &a.sky, &a.skz, &a.sL, &a.sLth, &a.resA, &a.resB, &a.resS, &a.fuseU,
+                       &a.fuseThr})
+        take(*d, nslots);
+    for (int** d : {&a.sell, &a.snscatt, &a.sstellar, &a.sstate, &a.svcell}) take(*d, nslots);
+    for (uint32_t** d : {&a.splo, &a.sphi, &a.sblock, &a.sw2, &a.sw3, &a.shave}) take(*d, nslots);
+    take(a.act[0], nslots);
+    take(a.act[1], nslots);
+    a.pathBuf = nullptr;
+    a.pathCnt = nullptr;
+    if (path) {
+        p = reinterpret_cast<char*>(((uintptr_t)p + 15) & ~(uintptr_t)15);
+        take(a.pathBuf, nslots * kPathCap);
+        take(a.pathCnt, nslots);
+    }
+    return bytes;
+}
+
 int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair) {
     const int ninstr = (int)c->instr.size();
     const size_t rays = (size_t)nslots * (1 + ninstr) + (continuous ? (size_t)nslots * kPathCap * ninstr : 0);
     if (rays >= (size_t)INT32_MAX) return fail(c, SKIRT_ERR_UNSUPPORTED, "ray queue too large");
     const int rayCap = (int)rays;
-    const size_t path = continuous ? (size_t)nslots * (kPathCap * sizeof(PathRec) + sizeof(int)) : 0;
-    const size_t bytes = (size_t)rayCap * sizeof(RayRec) + (detPair ? 2 : 1) * (size_t)(rayCap - nslots) * sizeof(DetRec) +
-                         (size_t)nslots * (13 * 8 + 5 * 4 + 6 * 4 + 2 * 4) + path + 4096;
-    if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolPath == (path > 0) && c->poolDetPair == detPair)
+    const bool path = continuous && nslots > 0;
+    if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolPath == path && c->poolDetPair == detPair)
         return SKIRT_OK;
-    c->poolPath = path > 0;
+    Args counted{};
+    const size_t bytes = poolLayout(nullptr, (size_t)nslots, (size_t)rayCap, detPair, path, counted) + kPoolSpare;
+    c->poolPath = path;
     c->poolDetPair = detPair;
     if (c->dPool) { (void)hipFree(c->dPool); c->dPool = nullptr; }
     HIPCHECK(c, hipMalloc(&c->dPool, bytes));
@@ -3606,28 +2182,7 @@ int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair) {
 }
 
 void carvePool(SkirtMcrt* c, Args& a) {
-    char* p = static_cast<char*>(c->dPool);
-    const size_t n = (size_t)c->nslots;
-    auto takeD = [&](double*& d) { d = reinterpret_cast<double*>(p); p += n * 8; };
-    auto takeI = [&](int*& d) { d = reinterpret_cast<int*>(p); p += n * 4; };
-    auto takeU = [&](uint32_t*& d) { d = reinterpret_cast<uint32_t*>(p); p += n * 4; };
-    a.rays = reinterpret_cast<RayRec*>(p);
-    p += (size_t)c->rayCap * sizeof(RayRec);
-    a.det = reinterpret_cast<DetRec*>(p);  // at most one peel-off per instrument and slot per iteration
-    p += (c->poolDetPair ? 2 : 1) * (size_t)(c->rayCap - c->nslots) * sizeof(DetRec);
-    takeD(a.srx); takeD(a.sry); takeD(a.srz); takeD(a.skx); takeD(a.sky); takeD(a.skz); takeD(a.sL); takeD(a.sLth);
-    takeD(a.resA); takeD(a.resB); takeD(a.resS); takeD(a.fuseU); takeD(a.fuseThr);
-    takeI(a.sell); takeI(a.snscatt); takeI(a.sstellar); takeI(a.sstate); takeI(a.svcell);
-    takeU(a.splo); takeU(a.sphi); takeU(a.sblock); takeU(a.sw2); takeU(a.sw3); takeU(a.shave);
-    takeI(a.act[0]); takeI(a.act[1]);
-    a.pathBuf = nullptr;
-    a.pathCnt = nullptr;
-    if (c->poolPath) {
-        p = reinterpret_cast<char*>(((uintptr_t)p + 15) & ~(uintptr_t)15);
-        a.pathBuf = reinterpret_cast<PathRec*>(p);
-        p += n * kPathCap * sizeof(PathRec);
-        takeI(a.pathCnt);
-    }
+    poolLayout(static_cast<char*>(c->dPool), (size_t)c->nslots, (size_t)c->rayCap, c->poolDetPair, c->poolPath, a);
     a.nslots = c->nslots;
     a.rayCap = c->rayCap;
     a.ctr = c->dCtr;
@@ -3740,121 +2295,7 @@ int ensureLeafMap(SkirtMcrt* c) {
     return SKIRT_OK;
 }
 
-// ================================================================== setup: density sampling
-// The setup's hot loop (skirt_mcrt_sample_density): one thread per item (a cell or a tree node), its
-// samples in order, so that every sum is accumulated as the host loop accumulates it (build.cpp cell
-// densities and tree subdivision). The geometry densities follow the host's Geometry::density operation
-// for operation (PlummerGeometry.cpp:49-54, ExpDiskGeometry::density, SersicGeometry::density with the
-// SersicFunction log-log interpolation, PointGeometry).
-struct DensArgs {
-    int ncomp, ntab, nsample, mode;
-    const int* kind;
-    const double* param;  // ncomp x 8
-    const double* norm;   // ncomp
-    const double* table;  // ncomp x 2 ntab
-    const double* boxes;  // n x 6
-    const uint32_t* words;
-    double* out;
-    size_t n;
-};
-
-__device__ double geomDensity(const DensArgs& d, int h, double x, double y, double z) {
-    const double* p = d.param + 8 * h;
-    switch (d.kind[h]) {
-    case SKIRT_GEOM_PLUMMER: {
-        const double r = sqrt(x * x + y * y + z * z);
-        const double s = r / p[0];
-        return p[1] * pow(1.0 + s * s, -2.5);
-    }
-    case SKIRT_GEOM_EXPDISK: {
-        const double R = sqrt(x * x + y * y);
-        const double absz = fabs(z);
-        const double hR = p[0], hz = p[1], Rmax = p[2], zmax = p[3], Rmin = p[4], rho0 = p[5];
-        if (Rmax > 0.0 && R > Rmax) return 0.0;
-        if (zmax > 0.0 && absz > zmax) return 0.0;
-        if (R < Rmin) return 0.0;
-        return rho0 * exp(-R / hR) * exp(-absz / hz);
-    }
-    case SKIRT_GEOM_SERSIC: {
-        const double r = sqrt(x * x + y * y + z * z);
-        const double s = r / p[0];
-        const double* sv = d.table + (size_t)2 * d.ntab * h;
-        const double* Sv = sv + d.ntab;
-        const int Ns = d.ntab;
-        if (s <= sv[0]) return p[2] * Sv[0];
-        if (s >= sv[Ns - 1]) return p[2] * Sv[Ns - 1];
-        int jl = -1, ju = Ns - 1;  // NR::locate_clip (s >= sv[0] here)
-        while (ju - jl > 1) {
-            const int jm = (ju + jl) >> 1;
-            if (s < sv[jm]) ju = jm;
-            else jl = jm;
-        }
-        // NR::interpolate_loglog
-        const double lx = log10(s), x1 = log10(sv[jl]), x2 = log10(sv[jl + 1]);
-        double f1 = Sv[jl], f2 = Sv[jl + 1];
-        const bool logf = f1 > 0 && f2 > 0;
-        if (logf) { f1 = log10(f1); f2 = log10(f2); }
-        double fx = f1 + ((lx - x1) / (x2 - x1)) * (f2 - f1);
-        if (logf) fx = pow(10.0, fx);
-        return p[2] * fx;
-    }
-    case SKIRT_GEOM_POINT:
-        return (x * x + y * y + z * z) == 0 ? INFINITY : 0.0;
-    default:  // the six closed-form kinds (geom_sample.hpp)
-        return geomDensityOf(d.kind[h], p, d.table ? d.table + (size_t)2 * d.ntab * h : nullptr, x, y, z);
-    }
-}
-
-// Geometry::generatePosition of one source component on fresh per-packet streams (skirt_mcrt_sample_positions):
-// the routines Events::launchStellar runs, one packet per thread
-__global__ void __launch_bounds__(kBlock)
-    samplePositionsKernel(const double* geomParam, const double* geomTable, int h, unsigned long long seed,
-                          unsigned long long first, size_t n, double* pos, int* draws, unsigned* error) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    PacketRng rng;
-    rng.start(seed, SKIRT_POSITIONS_TAG, first + i);
-    double x = 0.0, y = 0.0, z = 0.0;
-    if (!Events<SKIRT_GRID_CARTESIAN, true>::launchPosition(geomParam + 8 * h, geomTable, h, rng, x, y, z))
-        atomicOr(error, ERR_GEOM);
-    pos[3 * i] = x; pos[3 * i + 1] = y; pos[3 * i + 2] = z;
-    draws[i] = (int)(2u * rng.block - (rng.have ? 1u : 0u));
-}
-
-__global__ void __launch_bounds__(kBlock) densitySampleKernel(const DensArgs d) {
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= d.n) return;
-    const double* b = d.boxes + 6 * q;
-    const uint32_t* w = d.words + (size_t)3 * d.nsample * q;
-    constexpr double kWordMax = 4294967295.0;  // MTRandom::deviate
-    if (d.mode == SKIRT_DENS_COMPONENTS) {
-        double* o = d.out + (size_t)d.ncomp * q;
-        for (int h = 0; h < d.ncomp; h++) o[h] = 0.0;
-        for (int k = 0; k < d.nsample; k++) {
-            const double fx = (double)w[3 * k] / kWordMax, fy = (double)w[3 * k + 1] / kWordMax,
-                         fz = (double)w[3 * k + 2] / kWordMax;
-            const double x = b[0] + fx * (b[3] - b[0]), y = b[1] + fy * (b[4] - b[1]), z = b[2] + fz * (b[5] - b[2]);
-            for (int h = 0; h < d.ncomp; h++) o[h] += d.norm[h] * geomDensity(d, h, x, y, z);
-        }
-    } else {
-        double sum = 0, sx = 0, sy = 0, sz = 0, mn = 0, mx = 0;
-        for (int k = 0; k < d.nsample; k++) {
-            const double fx = (double)w[3 * k] / kWordMax, fy = (double)w[3 * k + 1] / kWordMax,
-                         fz = (double)w[3 * k + 2] / kWordMax;
-            const double x = b[0] + fx * (b[3] - b[0]), y = b[1] + fy * (b[4] - b[1]), z = b[2] + fz * (b[5] - b[2]);
-            double rho = 0;
-            for (int h = 0; h < d.ncomp; h++) rho += d.norm[h] * geomDensity(d, h, x, y, z);
-            sum += rho;
-            sx += rho * x;
-            sy += rho * y;
-            sz += rho * z;
-            if (k == 0 || rho < mn) mn = rho;  // std::min_element / max_element: the first extreme
-            if (k == 0 || mx < rho) mx = rho;
-        }
-        double* o = d.out + 6 * q;
-        o[0] = sum; o[1] = sx; o[2] = sy; o[3] = sz; o[4] = mn; o[5] = mx;
-    }
-}
+#include "density_sample.hpp"
 
 }  // namespace
 
@@ -4969,7 +3410,7 @@ static int runIterations(SkirtMcrt* c, const PhasePlan& pl) {
         }
         hipLaunchKernelGGL(detectKernel, dim3(pl.dgrid), dim3(kBlock), pl.ldsDetect, sd, d);
         HIPCHECK(c, hipGetLastError());
-        HIPCHECK(c, hipMemsetAsync(CTRP(d.ctr, 5 + d.parity), 0, sizeof(unsigned int), sd));
+        HIPCHECK(c, hipMemsetAsync(CTRP(d.ctr, CTR_DET + d.parity), 0, sizeof(unsigned int), sd));
         if (pl.detAside) {
             HIPCHECK(c, hipEventRecord(c->evDet[d.parity], sd));
             detUsed[d.parity] = true;
@@ -4989,9 +3430,10 @@ static int runIterations(SkirtMcrt* c, const PhasePlan& pl) {
             if (polls >= kPollRing) {
                 // the copy made kPollRing polls ago: is the phase finished?
                 HIPCHECK(c, hipEventSynchronize(pe));
-                if (CTR(hc, 2 + (pollIt[slot] & 1)) == 0) break;
+                if (CTR(hc, CTR_ACTIVE + (pollIt[slot] & 1)) == 0) break;
             }
-            HIPCHECK(c, hipMemcpyAsync(hc, aa.ctr, 8 * kCtrStride * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+            // (the counters before CTR_WALK; the poll reads CTR_ACTIVE)
+            HIPCHECK(c, hipMemcpyAsync(hc, aa.ctr, CTR_WALK * kCtrStride * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
             HIPCHECK(c, hipEventRecord(pe, st));
             pollIt[slot] = its;
             polls++;

@@ -2,7 +2,7 @@
 // ShellGeometry, GammaGeometry, GaussianGeometry, TTauriDiskGeometry, TorusGeometry and ConicalShellGeometry
 // (SKIRTcore/*.cpp of the same names), with SpecialFunctions::gln / gln2 / gexp (SpecialFunctions.cpp:754-791) and
 // Random::gauss (Random.cpp:140-150), in the reference's f64 operations, order and draw order. The same text
-// compiles for gfx950 (engine.hip: Events::launchStellar, geomDensity, samplePositionsKernel) and as plain C++
+// compiles for gfx950 (engine.hip: Events::launchStellar; density_sample.hpp: geomDensity, samplePositionsKernel) and as plain C++
 // (tools/geom_sample_cpu.py, the CPU logic test), so it touches nothing of the engine: parameters come in as the
 // component's row of SkirtSourceDesc::geom_param (7 doubles) and, for the torus and the cone, the first words of
 // its row of geom_table / dens_table; the random numbers come from any object with a uniform().

@@ -1,7 +1,7 @@
 // The paths of a ray through the two spherical dust grids: Sphere1DDustGrid::path
 // (SKIRTcore/Sphere1DDustGrid.cpp:111-187) and Sphere2DDustGrid::path (SKIRTcore/Sphere2DDustGrid.cpp:186-359),
 // each as an entry function, a step function and a whichcell, in the reference's f64 operations and order. The
-// same text compiles for gfx950 (engine.hip, Grid<SKIRT_GRID_SPHERE1D>, Grid<SKIRT_GRID_SPHERE2D>) and as plain
+// same text compiles for gfx950 (grid_mesh2d.hpp, Grid<SKIRT_GRID_SPHERE1D>, Grid<SKIRT_GRID_SPHERE2D>) and as plain
 // C++ (tools/sph_walk_cpu.py, the CPU logic test), so it touches nothing of the engine: borders come in as plain
 // arrays (LDS on the device), segments leave through a callable or by reference.
 //

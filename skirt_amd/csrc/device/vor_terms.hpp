@@ -1,5 +1,5 @@
 // The stored neighbour entries and per-cell error terms of the compact Voronoi step's single-precision bounds
-// (engine.hip, Grid<SKIRT_GRID_VORONOI>::bounds), shared by the engine's Voronoi upload and the host
+// (grid_voronoi.hpp, Grid<SKIRT_GRID_VORONOI>::bounds), shared by the engine's Voronoi upload and the host
 // exactness check (tools/vor_compact_check.cpp).
 //
 // For a neighbour offset n (scaled, rounded to float), the float evaluation of n.k and of n.D + |n|^2/2

@@ -25,7 +25,7 @@ def checker(tmp_path_factory):
 
 # the checker's modes: n -- double bounds; f -- the round-2 float bounds; x -- per-entry Cauchy-Schwarz
 # terms; d -- the cell's largest terms from its header on the offsets n (round 3); r -- the device's step
-# (engine.hip Grid<SKIRT_GRID_VORONOI>::bounds: entries m = n / |n|^2 and the cell's terms, both computed by
+# (grid_voronoi.hpp Grid<SKIRT_GRID_VORONOI>::bounds: entries m = n / |n|^2 and the cell's terms, both computed by
 # the engine's own vor_terms.hpp); r+ / r- / r~ -- the device's step with its approximate reciprocal
 # (v_rcp_f32, 1 ulp) emulated: every reciprocal one ulp up, down, or each by a random -1 / 0 / +1 ulp
 @pytest.mark.parametrize("mode", ["n", "f", "x", "d", "r", "r+", "r-", "r~"],

@@ -2,8 +2,8 @@
 // would the trace kernel issue for one launch's FILL rays under different ray orders and merge schemes?
 //
 // The FILL paths come from the oracle (Philox streams, the engine's packets) through oracle_set_fill_hook;
-// cells are renumbered as the engine numbers device cells (engine.hip: depth-first octant order, groups of
-// 8 sibling leaves aligned to one 64-byte line of a Labs row). Then a model of the persistent trace kernel
+// cells are renumbered as the engine numbers device cells (numberTreeLeaves on engine.hip's host side:
+// depth-first octant order, groups of 8 sibling leaves aligned to one 64-byte line of a Labs row). Then a model of the persistent trace kernel
 // (W waves of 64 lanes, one segment per lane-step, 64-ray pull chunks handed round robin to the waves,
 // kLabsBuf = 16 adds buffered per lane) counts requests for:
 //   run     consecutive adds of one ray in one line share a request (the engine's own count, 1.85 on C3)
@@ -60,7 +60,7 @@ void hook(void* user, int ell, const double r[3], const double k[3], const int* 
     s->rays.push_back(y);
 }
 
-// engine.hip's octree device numbering (upload of SKIRT_GRID_OCTREE)
+// the engine's octree device numbering (numberTreeLeaves in engine.hip's host side, upload of SKIRT_GRID_OCTREE)
 std::vector<int> deviceCells(const skirt::OctreeGrid& g, int ncells) {
     std::vector<int> dev(ncells, -1);
     std::vector<int> stack{0};

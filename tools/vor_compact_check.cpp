@@ -1,5 +1,5 @@
 // Host check of the compact Voronoi step (float neighbour offsets + exact winner), the arithmetic that
-// Grid<SKIRT_GRID_VORONOI>::step in engine.hip runs: walks random rays through a tessellation twice,
+// Grid<SKIRT_GRID_VORONOI>::step in grid_voronoi.hpp runs: walks random rays through a tessellation twice,
 // once with the reference's step (VoronoiMesh::path, VoronoiMesh.cpp:749-844, double sites) and once with
 // the compact step (interval bounds from float offsets, the exact reference expression for the winner,
 // exact re-evaluation of every possible winner when the bounds cannot separate them), and requires the
@@ -155,13 +155,13 @@ static int compactStepF(const Mesh& M, int m, const double r[3], const double k[
         const int mi = g.cell_nbr_list[q];
         const float nx = M.off[3 * (size_t)q], ny = M.off[3 * (size_t)q + 1], nz = M.off[3 * (size_t)q + 2];
         if (gDevice) {
-            // Grid<SKIRT_GRID_VORONOI>::bounds (engine.hip) operation for operation: the error terms from
+            // Grid<SKIRT_GRID_VORONOI>::bounds (grid_voronoi.hpp) operation for operation: the error terms from
             // the cell's largest |n|_1 and |n|^2 (the header's eA, eB; mode x: per entry, as in round 3's
             // first version)
             const float Dn = fabsf(Dx) + fabsf(Dy) + fabsf(Dz);
             const float n2 = fmaf(nz, nz, fmaf(ny, ny, nx * nx));
             const float den = fmaf(nz, kz, fmaf(ny, ky, nx * kx));
-            // mode r (engine.hip bounds()): (m.D + 1/2) / (m.k), the entries being m
+            // mode r (grid_voronoi.hpp bounds()): (m.D + 1/2) / (m.k), the entries being m
             const float num = gRecip ? fmaf(nz, Dz, fmaf(ny, Dy, fmaf(nx, Dx, 0.5f)))
                                      : fmaf(n2, 0.5f, fmaf(nz, Dz, fmaf(ny, Dy, nx * Dx)));
             const float eA = gPerEntry ? kEpsF * (fabsf(nx) + fabsf(ny) + fabsf(nz)) : M.eA[m];
@@ -269,7 +269,7 @@ int main(int argc, char** argv) {
     for (int m = 0; m < N; m++)
         if (g.cell_nbr_offset[m + 1] - g.cell_nbr_offset[m] > 4096) { fprintf(stderr, "neighbour list too long\n"); return 1; }
     M.off.assign(3 * (size_t)nn, 0.f);
-    // scaled float offsets as the device stores them (engine.hip, Voronoi upload): walls as the offset to
+    // scaled float offsets as the device stores them (engine.hip's host side, uploadVoronoi): walls as the offset to
     // the site's mirror image
     for (int m = 0; m < N; m++)
         for (int q = g.cell_nbr_offset[m]; q < g.cell_nbr_offset[m + 1]; q++) {
