@@ -114,6 +114,22 @@ int skirt_sim_describe(SkirtSim* sim, const char* path);
 int skirt_host_write_descriptors(const char* path, const SkirtGridDesc* grid, const SkirtMediaDesc* media,
                                  const SkirtSourceDesc* sources, const SkirtInstrDesc* instr, int ninstr);
 
+/* appends a polarising model's SkirtMuellerDesc in the same form (fields mueller.*), followed by the four 361-entry
+ * phi tables of DustMix::setupSelfAfter as the engine builds them; skirt_sim_describe calls it for polarising
+ * models only, so the dumps of the others stay as they were */
+int skirt_host_write_mueller(const char* path, const SkirtMuellerDesc* mueller);
+
+/* 1 if the simulation's dust mixes polarise (DustSystem::polarization; ElectronDustMix), else 0: its packets then
+ * carry Stokes vectors and every FullInstrument has three more slots, Stokes Q, U, V, after its scattering levels
+ * (files _stokesQ/U/V.fits, SED columns 8-10) */
+int skirt_sim_polarization(SkirtSim* sim);
+/* One scattering and one scattering peel-off towards instrument `instrument` of n given packet states
+ * (skirt_mcrt_scatterings, which documents the 12 words of a state, the 2 deviates and the 14 words of a result): on
+ * the attached engine of HIP device `device` (which must be the device of skirt_sim_attach; another one is
+ * SKIRT_ERR_ARG), or with device < 0 by the host's compilation of the same routines (device/polarization.hpp). */
+int skirt_sim_scatterings(SkirtSim* sim, int instrument, int device, size_t n, const double* states,
+                          const double* deviates, double* out);
+
 /* Random positions of stellar component `comp` (skirt_mcrt_sample_positions): on the attached engine of HIP
  * device `device` (which must be the device of skirt_sim_attach), or with device < 0 on the host, through the
  * host's position templates on the same per-packet streams. pos is n x 3, draws n (or NULL). */

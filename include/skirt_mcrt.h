@@ -20,7 +20,8 @@
  * Layouts: Labs is row-major (cell, wavelength) like DustSystem::_Labs*vv (Table.hpp:104-105).
  * Instrument tallies (as downloaded) are per instrument [nslots][nlambda][nframe] frames followed by
  * [nslots][nlambda] SEDs, slots as in FullInstrument (trav, strdir, strsca, dusdir, dussca,
- * scattering levels...) or a single "total" slot for Simple/SED/Frame instruments. These are host
+ * scattering levels..., then Stokes Q, U, V with skirt_mcrt_set_mueller) or a single "total" slot for
+ * Simple/SED/Frame instruments. These are host
  * layouts: the device buffers (skirt_mcrt_tally_sizes, bind_tallies) are wavelength-major with padded
  * rows and are converted by the downloads.
  */
@@ -330,6 +331,31 @@ int skirt_mcrt_sample_density(int device, const SkirtDensityDesc* dens, const do
 #define SKIRT_POSITIONS_TAG 0x504f5331u
 int skirt_mcrt_sample_positions(SkirtMcrt* ctx, int comp, uint64_t seed, uint64_t first, size_t n, double* pos,
                                 int32_t* draws);
+
+/* Polarised scattering (StokesVector.cpp; DustMix.cpp:96-140, 541-670, 716-731; MonteCarloSimulation.cpp:347-360;
+ * FullInstrument.cpp:79-87, 136-141): per dust component its Mueller matrix elements at ntheta scattering angles
+ * theta_t = t pi / (ntheta - 1) and what DustMix::setupSelfAfter derives from them, all ncomp x nlambda x ntheta
+ * row-major but pfnorm (ncomp x nlambda). The engine is general in the tables; it adds the 361-entry phi tables
+ * itself. With tables set, every packet of a stellar phase with dust carries a Stokes vector, scatters by the tables,
+ * and every FullInstrument has three more slots -- Stokes Q, U, V, after its scattering-level slots -- in the tallies
+ * (so call it after upload_media and before set_instruments). A polarised context refuses continuous scattering
+ * and the dust phases (SKIRT_ERR_UNSUPPORTED). NULL, or never calling it, means unpolarised. */
+typedef struct {
+    int ncomp, nlambda, ntheta;
+    const double *S11, *S12, *S33, *S34;
+    const double* thetaX;       /* NR::cdf over S11(t+1) sin theta(t+1) dt */
+    const double* pfnorm;       /* 2 / sum_t S11(t) sin theta(t) dt */
+} SkirtMuellerDesc;
+int skirt_mcrt_set_mueller(SkirtMcrt* ctx, const SkirtMuellerDesc* mueller);
+
+/* What one scattering and one scattering peel-off towards instrument `instrument` make of n given packet states, by
+ * the event kernel's routines (polarization.hpp). states[12 i ..] = {kx, ky, kz, Q, U, V, nx, ny, nz, polarized (0 or
+ * 1), ell, comp}: direction, Stokes parameters normalized by I, normal of the scattering plane, flag, wavelength
+ * and dust component; deviates[2 i ..]: the two uniform deviates of the scattering (theta's, then phi's).
+ * out[14 i ..] = direction, Q, U, V, normal and flag after the scattering by component comp, then I and Q/I, U/I, V/I
+ * of the peel-off from the state before that scattering, with that component at weight 1. Synchronous. */
+int skirt_mcrt_scatterings(SkirtMcrt* ctx, int instrument, size_t n, const double* states, const double* deviates,
+                           double* out);
 
 /* The cells of a Voronoi tessellation on HIP device `device` (setup, §8(f)2; the reference computes them with
  * Voro++, VoronoiMesh.cpp:310-376): the host construction of skirt_host_voronoi_build (the domain box clipped

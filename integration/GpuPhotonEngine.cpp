@@ -377,7 +377,11 @@ void GpuPhotonEngine::describeMedia()
     for (int h = 0; h < Ncomp; h++)
     {
         DustMix* mix = _ds->mix(h);
-        if (mix->polarization()) throw FATALERROR("MI355X engine: polarized dust mixes are not supported");
+        // (DustMix keeps its Mueller tables private, so the binding cannot hand them to skirt_mcrt_set_mueller; passing
+        // such a mix on as Henyey-Greenstein with g = 0 would run it wrongly. The .ski driver does pass them.)
+        if (mix->polarization())
+            throw FATALERROR("MI355X engine: polarized dust mixes are not supported by this binding "
+                             "(DustSystem::polarization() is true; the Mueller tables are private to DustMix)");
         for (int ell = 0; ell < _Nlambda; ell++)
         {
             kext[h * _Nlambda + ell] = mix->kappaext(ell);

@@ -76,6 +76,8 @@ ABI_SYMBOLS = [
     "skirt_rccl_create", "skirt_rccl_wrap", "skirt_rccl_rank", "skirt_rccl_reducer", "skirt_rccl_abort", "skirt_rccl_destroy", "skirt_sim_describe", "skirt_host_write_descriptors",
     "skirt_sim_run_devices", "skirt_mcrt_voronoi_cells", "skirt_host_voronoi_build_ex", "skirt_host_voronoi_cells",
     "skirt_mcrt_sample_positions", "skirt_sim_sample_positions",
+    "skirt_mcrt_set_mueller", "skirt_mcrt_scatterings", "skirt_sim_polarization", "skirt_sim_scatterings",
+    "skirt_host_write_mueller",
 ]
 
 _lib = None
@@ -136,6 +138,11 @@ def lib():
                                                      ctypes.POINTER(c_dbl), ctypes.POINTER(ctypes.c_int32)]
             L.skirt_mcrt_sample_positions.argtypes = [vp, c_int, c_u64, c_u64, ctypes.c_size_t, ctypes.POINTER(c_dbl),
                                                       ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "skirt_sim_scatterings"):  # (likewise)
+            L.skirt_sim_polarization.argtypes = [vp]
+            L.skirt_sim_scatterings.argtypes = [vp, c_int, c_int, ctypes.c_size_t] + [ctypes.POINTER(c_dbl)] * 3
+            L.skirt_mcrt_scatterings.argtypes = [vp, c_int, ctypes.c_size_t] + [ctypes.POINTER(c_dbl)] * 3
+            L.skirt_mcrt_set_mueller.argtypes = [vp, vp]
         L.skirt_sim_error.restype = ctypes.c_char_p
         L.skirt_sim_free.argtypes = [vp]
         L.skirt_mcrt_stats.argtypes = [vp, ctypes.POINTER(SkirtStats)]
@@ -328,6 +335,39 @@ class Simulation:
             self._h, int(comp), -1 if device is None else int(device), int(seed), int(first), n,
             pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), draws.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return pos, draws
+
+    @property
+    def polarization(self):
+        """True when the dust mixes polarise (ElectronDustMix): packets carry Stokes vectors and every
+        FullInstrument has three more slots, Stokes Q, U, V, after its scattering levels."""
+        return bool(lib().skirt_sim_polarization(self._h))
+
+    def stokes(self, i):
+        """(frames [3, nlambda, nframe] or None, seds [3, nlambda]): Stokes Q, U, V of FullInstrument i of a polarised
+        simulation; (None, None) for any other instrument or simulation."""
+        frames, seds = self.instrument(i)
+        if not self.polarization or seds is None or len(seds) < 8:  # (a FullInstrument's 5 slots + levels + 3)
+            return None, None
+        return (None if frames is None else frames[-3:]), seds[-3:]
+
+    def scatterings(self, states, deviates, instrument, device=None):
+        """What one scattering and one scattering peel-off towards instrument `instrument` make of packet states
+        [n, 12] = (kx, ky, kz, Q, U, V, nx, ny, nz, polarized, ell, comp) with the uniform deviates [n, 2] (theta's,
+        phi's): results [n, 14] = direction, Q, U, V, normal and polarized flag after the scattering by component
+        comp, then I and Q/I, U/I, V/I of the peel-off from the state before it (include/skirt_mcrt.h,
+        skirt_mcrt_scatterings). device=None runs the host's compilation of the engine's routines; a device runs
+        them there (attaching to it when no engine is attached yet)."""
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 12)
+        dv = np.ascontiguousarray(deviates, dtype=np.float64).reshape(-1, 2)
+        if len(st) != len(dv):
+            raise SkirtError("scatterings: %d states but %d pairs of deviates" % (len(st), len(dv)))
+        out = np.zeros((len(st), 14))
+        if device is not None and not self.attached:
+            self.attach(int(device))
+        P = ctypes.POINTER(ctypes.c_double)
+        self._check(lib().skirt_sim_scatterings(self._h, int(instrument), -1 if device is None else int(device), len(st),
+                                                st.ctypes.data_as(P), dv.ctypes.data_as(P), out.ctypes.data_as(P)))
+        return out
 
     def stats(self):
         s = SkirtStats()

@@ -49,7 +49,10 @@ __device__ __forceinline__ void detectPeel(const Args& a, const DevInstr& ins, u
     }
 }
 
-// the detections of this iteration's peel-off rays (their optical depths are in the queue now)
+// the detections of this iteration's peel-off rays (their optical depths are in the queue now).
+// POL: a FullInstrument's three Stokes slots (DevInstr::stokes ..) receive Lextf Q, Lextf U, Lextf V of every
+// detection, whatever its category (FullInstrument.cpp:136-141, 165-170); POL = false is the kernel as it was
+template <bool POL>
 __global__ void __launch_bounds__(kBlock) detectKernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const unsigned int nrays = CTR(a.ctr, CTR_DET + a.parity);  // this iteration's
@@ -78,7 +81,10 @@ __global__ void __launch_bounds__(kBlock) detectKernel(const Args a) {
         const double Lp = d.Lp, Lextf = Lp * exp(-d.tau);
         for (int slot = sub; slot < ins.nslots; slot += 8) {
             double v;
-            if (!detectSlot(ins, flags, slot, Lp, Lextf, v)) continue;
+            if (POL && ins.stokes > 0 && slot >= ins.stokes) {
+                const DetPol q = a.detPol[id];
+                v = Lextf * (slot == ins.stokes ? q.Q : (slot == ins.stokes + 1 ? q.U : q.V));
+            } else if (!detectSlot(ins, flags, slot, Lp, Lextf, v)) continue;
             if (ins.kind != SKIRT_INSTR_FRAME) {
                 if (sed) atomicAdd(&sed[ins.sedOff + slot * a.nlambda + ell], v);
                 else atomicAddF64(a.tally + ins.sedBase + slot * a.nlambda + ell, v);

@@ -37,6 +37,7 @@
 #include "cyl2d_walk.hpp"
 #include "sph_walk.hpp"
 #include "geom_sample.hpp"
+#include "polarization.hpp"
 #include "../../../include/skirt_mcrt.h"
 #include "philox.hpp"
 
@@ -95,12 +96,16 @@ constexpr int kPollRing = 3;       // copies in flight (the host reads each kPol
 #ifndef SKIRT_EVENT_WAVES  // (variant builds)
 #define SKIRT_EVENT_WAVES 2
 #endif
-#define SKIRT_EVENT_ATTR __attribute__((amdgpu_waves_per_eu(SKIRT_EVENT_WAVES)))
+// One instantiation runs at 1: polarised with several components on a Voronoi grid. It needs 278 registers (256
+// VGPRs + 22 AGPRs); held to 2 waves it keeps 96 bytes of scratch per lane ("Registers")
+#define SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, POL) \
+    __attribute__((amdgpu_waves_per_eu(((POL) && !(ONECOMP) && (GRID) == SKIRT_GRID_VORONOI) ? 1 : SKIRT_EVENT_WAVES)))
 
 // ------------------------------------------------------------------ descriptors
 struct DevInstr {
     int kind, nx, ny, nslots, levels, sedOff;  // sedOff: offset of this instrument's SEDs in the LDS sums
-    int slotStride, pad;                        // frames: slots per pixel, padded (see frameAt)
+    int slotStride, stokes;                     // frames: slots per pixel, padded (see frameAt); the first of the
+                                                //   Stokes Q, U, V slots of a polarised simulation (0: none)
     long long frameBase;                        // offset of the frames in the global instrument tally
     long long sedBase;                          // offset of the SEDs in the global instrument tally
     double kobs[3];
@@ -169,6 +174,10 @@ struct __attribute__((aligned(16))) DetRec {
     unsigned flags;        // as the ray's flags
 };
 static_assert(sizeof(DetRec) == 24 || sizeof(DetRec) == 32, "detection record layout");
+// beside it in a polarised phase, in an array of its own: Q/I, U/I, V/I of the peel-off (0 for an emission peel-off)
+struct DetPol {
+    double Q, U, V;
+};
 __device__ __forceinline__ unsigned rayMode(unsigned f) { return f & 3u; }
 __device__ __forceinline__ unsigned rayCat(unsigned f) { return (f >> 2) & 3u; }
 __device__ __forceinline__ int rayInstr(unsigned f) { return (int)((f >> 4) & 63u); }
@@ -428,6 +437,14 @@ struct Args {
     int* pathCnt;
     int ldsMeshOff, ldsOptOff, ldsInstrOff, ldsSedOff;  // in doubles
     int detCopies;  // detect kernel: LDS copies of the SED sums (8, 4, 2, 1), 0 = SEDs straight to the tally
+    // polarised scattering (skirt_mcrt_set_mueller; pol == 0: none of these is read): the mixes' tables in global
+    // memory (polarization.hpp, polTableWords), per slot the packet's Stokes vector, the normal of its scattering
+    // plane and its polarized flag, and the detection records' Stokes parameters
+    int pol, polNtheta;
+    const double* polTab;
+    double *sQ, *sU, *sV, *snx, *sny, *snz;
+    int* spol;
+    DetPol* detPol;
 };
 
 // One finest-level cell of the octree leaf map: the leaf node that covers it, that leaf's dust cell
@@ -1039,9 +1056,18 @@ struct Packet {
     double rx, ry, rz, kx, ky, kz, L, Lth;
     int ell, nscatt, stellar, state;
     PacketRng rng;
+    PolStokes sv;  // POL kernels only
 };
 
-template <int GRID, bool ONECOMP>
+// the deviates of polScatter from the packet's stream
+struct PolDrawsStream {
+    PacketRng& rng;
+    __device__ __forceinline__ double uniform() { return rng.uniform(); }
+};
+
+// POL: a simulation whose dust mixes polarise (Args::pol): the packet carries a Stokes vector, scatters by the
+// Mueller tables and its peel-offs carry Q, U, V. POL = false is the code as it was.
+template <int GRID, bool ONECOMP, bool POL = false>
 struct Events {
     const Args& a;
     const Shared& sh;
@@ -1105,6 +1131,11 @@ struct Events {
         p.rng.k0 = (uint32_t)a.seed; p.rng.k1 = (uint32_t)(a.seed >> 32); p.rng.tag = a.tag;
         p.rng.plo = a.splo[s]; p.rng.phi = a.sphi[s]; p.rng.block = a.sblock[s];
         p.rng.w2 = a.sw2[s]; p.rng.w3 = a.sw3[s]; p.rng.have = a.shave[s];
+        if constexpr (POL) {
+            p.sv.Q = a.sQ[s]; p.sv.U = a.sU[s]; p.sv.V = a.sV[s];
+            p.sv.nx = a.snx[s]; p.sv.ny = a.sny[s]; p.sv.nz = a.snz[s];
+            p.sv.pol = a.spol[s];
+        }
     }
     __device__ __forceinline__ void store(int s, const Packet& p) const {
         a.srx[s] = p.rx; a.sry[s] = p.ry; a.srz[s] = p.rz;
@@ -1113,6 +1144,11 @@ struct Events {
         a.sell[s] = p.ell; a.snscatt[s] = p.nscatt; a.sstellar[s] = p.stellar; a.sstate[s] = p.state;
         a.splo[s] = p.rng.plo; a.sphi[s] = p.rng.phi; a.sblock[s] = p.rng.block;
         a.sw2[s] = p.rng.w2; a.sw3[s] = p.rng.w3; a.shave[s] = p.rng.have;
+        if constexpr (POL) {
+            a.sQ[s] = p.sv.Q; a.sU[s] = p.sv.U; a.sV[s] = p.sv.V;
+            a.snx[s] = p.sv.nx; a.sny[s] = p.sv.ny; a.snz[s] = p.sv.nz;
+            a.spol[s] = p.sv.pol;
+        }
     }
 
     __device__ __forceinline__ int pixel(const DevInstr& ins, const Packet& p) const {
@@ -1150,6 +1186,42 @@ struct Events {
             I += (wv * ((1.0 - g) * (1.0 + g) / sqrt(t * t * t))) * 1.0;
         }
         return true;
+    }
+
+    // the cell of the peel-off round, or -1 where peeloffscattering aborts (MonteCarloSimulation.cpp:332-337): no
+    // cell, or no scattering dust in it; m is whichcell of the packet's position
+    __device__ __forceinline__ int peelCell(const Packet& p, int m) const {
+        if (m == -1) return -1;
+        double sum = 0;
+        for (int h = 0; h < a.ncomp; h++) sum += sh.ksca[h * a.nlambda + p.ell] * rho(m, h);
+        return sum <= 0 ? -1 : m;
+    }
+
+    // The same with polarisation (MonteCarloSimulation.cpp:347-360): I and, as PhotonPackage::setPolarized leaves
+    // them, Q/I, U/I, V/I of the peel-off towards `ins` of a packet with direction k and Stokes vector sv, summed
+    // over the components with the weights wv[h] phaseFunctionValue; m is the round's peelCell (the packet has not
+    // moved since), so the grid is searched once per round and not once per instrument
+    __device__ __forceinline__ void peelWeightPol(const DevInstr& ins, const Packet& p, int m, double kx, double ky,
+                                                  double kz, const PolStokes& sv, double& I, DetPol& q) const {
+        // DistantInstrument::bfky (DistantInstrument.cpp:47-49)
+        const double yx = -ins.cosphi * ins.costheta * ins.cospa - ins.sinphi * ins.sinpa;
+        const double yy = -ins.sinphi * ins.costheta * ins.cospa + ins.cosphi * ins.sinpa;
+        const double yz = +ins.sintheta * ins.cospa;
+        I = 0;
+        q.Q = 0; q.U = 0; q.V = 0;
+        if (ONECOMP) {
+            const PolMix mx = polMixAt(a.polTab, a.ncomp, a.nlambda, a.polNtheta, 0, p.ell);
+            polPeelAdd(mx, 1.0, sv, kx, ky, kz, ins.kobs[0], ins.kobs[1], ins.kobs[2], yx, yy, yz, I, q.Q, q.U, q.V);
+        } else {
+            double sum = 0;
+            for (int h = 0; h < a.ncomp; h++) sum += sh.ksca[h * a.nlambda + p.ell] * rho(m, h);
+            for (int h = 0; h < a.ncomp; h++) {
+                const double wv = sh.ksca[h * a.nlambda + p.ell] * rho(m, h) / sum;
+                const PolMix mx = polMixAt(a.polTab, a.ncomp, a.nlambda, a.polNtheta, h, p.ell);
+                polPeelAdd(mx, wv, sv, kx, ky, kz, ins.kobs[0], ins.kobs[1], ins.kobs[2], yx, yy, yz, I, q.Q, q.U, q.V);
+            }
+        }
+        polPeelNormalize(I, q.Q, q.U, q.V);
     }
 
     // Instrument::detect without a dust system (tau = 0): FullInstrument then holds only the
@@ -1233,9 +1305,12 @@ struct Events {
     // simulatescattering: DustSystem::randomMixForPosition + DustMix::scatteringDirectionAndPolarization
     // (HG, DustMix.cpp:609-613) + Random::direction(k, costheta) (Random.cpp:188-222)
     __device__ __forceinline__ void scatter(Packet& p) const {
+        scatterIn(p, ONECOMP ? -1 : Grid<GRID>::whichcell(a, sh, p.rx, p.ry, p.rz));
+    }
+    // the same with whichcell of the packet's position given (not looked at with one component)
+    __device__ __forceinline__ void scatterIn(Packet& p, int m) const {
         int hmix = 0;
         if (!ONECOMP) {
-            const int m = Grid<GRID>::whichcell(a, sh, p.rx, p.ry, p.rz);
             if (m >= 0) {
                 double Xv[9];
                 Xv[0] = 0.0;
@@ -1245,6 +1320,13 @@ struct Events {
                 for (int h = 1; h < a.ncomp; h++)
                     if (Xv[h] / norm <= X) hmix = h;
             }
+        }
+        if constexpr (POL) {  // DustMix::scatteringDirectionAndPolarization, polarized (DustMix.cpp:586-606)
+            const PolMix mx = polMixAt(a.polTab, a.ncomp, a.nlambda, a.polNtheta, hmix, p.ell);
+            PolDrawsStream draws{p.rng};
+            polScatter(mx, p.kx, p.ky, p.kz, p.sv, draws);
+            p.nscatt++;
+            return;
         }
         const double g = sh.g[hmix * a.nlambda + p.ell];
         double nx, ny, nz;
@@ -1548,14 +1630,14 @@ __device__ __forceinline__ unsigned long long globalPacket(const Args& a, unsign
     return ell * a.npp + a.sliceLo + (j - ell * a.sliceCnt);
 }
 
-template <int GRID, bool ONECOMP>
-__global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Args a) {
+template <int GRID, bool ONECOMP, bool POL = false>
+__global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, POL) eventKernel(const Args a) {
     __shared__ unsigned long long resv[4 * (kBlock / 64) + 4];
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (blockIdx.x == 0 && threadIdx.x == 0) CTR(a.ctr, CTR_PULL) = 0;
     if (!a.init && CTR(a.ctr, CTR_ACTIVE + a.parity) == 0) return;  // an iteration after the end of the phase
     Shared sh = stageTables(a, lds, gridParts<GRID>() | STAGE_OPTICS | STAGE_INSTR);
-    Events<GRID, ONECOMP> E{a, sh};
+    Events<GRID, ONECOMP, POL> E{a, sh};
     const int lane = threadIdx.x & 63;
     const unsigned long long total = a.end - a.first;
     const unsigned int nwork = a.init ? (unsigned)a.nslots : CTR(a.ctr, CTR_ACTIVE + a.parity);
@@ -1592,6 +1674,9 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
         unsigned mainMode = RAY_NONE;
         double mainParam = 0;
         double ox = 0, oy = 0, oz = 0;  // direction before scattering (peel-off weights)
+        PolStokes osv;                  // and the Stokes vector (POL)
+        int pcell = -1;                 // and the cell of the peel-off round (POL, several components)
+        if constexpr (POL) polSetUnpolarized(osv);
         if (valid && !a.init) {
             if (p.state == S_FILL) {
                 // end of fillOpticalDepth + simulateescapeandabsorption; termination; simulatepropagation
@@ -1629,9 +1714,19 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
                 p.rz = p.rz + s * p.kz;
                 // peeloffscattering, unless the continuous peel-off replaces it (MonteCarloSimulation.cpp:291)
                 bool ok = a.ninstr > 0 && a.peel && !a.continuous;
-                if (ok && !ONECOMP) { double I; ok = E.peelWeight(sh.instr[0], p, p.kx, p.ky, p.kz, I); }
+                int scell = -1;  // POL, several components: the grid is searched once for the round and the scattering
+                if constexpr (POL) {
+                    if (!ONECOMP) {
+                        scell = Grid<GRID>::whichcell(a, sh, p.rx, p.ry, p.rz);
+                        if (ok) { pcell = E.peelCell(p, scell); ok = pcell >= 0; }
+                    }
+                    osv = p.sv;
+                } else {
+                    if (ok && !ONECOMP) { double I; ok = E.peelWeight(sh.instr[0], p, p.kx, p.ky, p.kz, I); }
+                }
                 if (ok) { peel = PEEL_SCATTER; ox = p.kx; oy = p.ky; oz = p.kz; }
-                E.scatter(p);
+                if constexpr (POL && !ONECOMP) E.scatterIn(p, scell);
+                else E.scatter(p);
                 mainMode = RAY_FILL;
                 mainParam = p.L;
                 p.state = S_FILL;
@@ -1649,6 +1744,7 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
                 if (idx >= total) need = false;  // exhausted: the slot retires
                 else if (E.launch(p, globalPacket(a, a.first + idx))) {
                     vcell = kNoCell;  // a new position
+                    if constexpr (POL) polSetUnpolarized(p.sv);  // PhotonPackage::launch
                     if (!(p.L > 0) && !a.crossed) {
                         // a zero-weight dust packet (a cell without emission drawn uniformly): every
                         // tally it would touch receives 0, so it ends here -- unless the cells-crossed
@@ -1724,11 +1820,14 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
                 const DevInstr& ins = sh.instr[i];
                 double Lp = p.L;
                 unsigned cat, level = 0;
+                DetPol dq{0.0, 0.0, 0.0};  // (an emission peel-off is unpolarized)
                 if (peel == PEEL_EMISSION) {
                     cat = p.stellar >= 0 ? CAT_STAR_DIRECT : CAT_DUST_DIRECT;
                 } else {
                     double I = 0;
-                    E.peelWeight(ins, p, ox, oy, oz, I);  // the direction before scattering
+                    // the direction (and the Stokes vector) before scattering
+                    if constexpr (POL) E.peelWeightPol(ins, p, pcell, ox, oy, oz, osv, I, dq);
+                    else E.peelWeight(ins, p, ox, oy, oz, I);
                     Lp = p.L * I;
                     cat = p.stellar >= 0 ? CAT_STAR_SCATTERED : CAT_DUST_SCATTERED;
                     level = (unsigned)min(p.nscatt, 255);  // nscatt already counts this scattering
@@ -1740,6 +1839,7 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR eventKernel(const Arg
                 // grid leaves tau = 0)
                 idx = (int)(dpos + k);
                 a.det[idx] = DetRec{Lp, 0.0, l, flags};
+                if constexpr (POL) a.detPol[idx] = dq;
                 at = pos++;
             } else {
                 dx = p.kx; dy = p.ky; dz = p.kz;
@@ -1936,6 +2036,11 @@ struct SkirtMcrt {
     // media
     int ncomp = 0, nlambda = 0;
     double *dRho = nullptr, *dOptics = nullptr;
+    // polarised scattering (skirt_mcrt_set_mueller): the mixes' tables as polarization.hpp lays them out, on the
+    // device and on the host (the probe's host side), and their theta resolution; null: unpolarised
+    double* dPolTab = nullptr;
+    std::vector<double> polTab;
+    int polNtheta = 0;
     // sources
     int nstar = 0;
     double *dGeomParam = nullptr, *dLum = nullptr, *dLumtot = nullptr, *dCdf = nullptr;
@@ -1986,6 +2091,7 @@ struct SkirtMcrt {
     int nslots = 0, rayCap = 0;
     bool poolPath = false;  // the pool holds the continuous-scattering path records
     bool poolDetPair = false;  // the pool holds two detection-record regions (one per iteration parity)
+    bool poolPol = false;      // the pool holds the Stokes arrays of a polarised simulation
     void* dPool = nullptr;               // nslots slots
     size_t poolBytes = 0;
     // config
@@ -2132,7 +2238,7 @@ static_assert(sizeof(RayRec) % 16 == 0 && alignof(RayRec) == 16 && sizeof(DetRec
                   alignof(PathRec) <= 16,
               "pool order: ray records, detection records, 8-byte arrays, 4-byte arrays, aligned path records");
 constexpr size_t kPoolSpare = 4096;
-size_t poolLayout(char* base, size_t nslots, size_t rayCap, bool detPair, bool path, Args& a) {
+size_t poolLayout(char* base, size_t nslots, size_t rayCap, bool detPair, bool path, bool pol, Args& a) {
     char* p = base;
     size_t bytes = 0;
     auto take = [&](auto*& d, size_t count) {
@@ -2147,6 +2253,16 @@ size_t poolLayout(char* base, size_t nslots, size_t rayCap, bool detPair, bool p
     for (double** d : {&a.srx, &a.sry, &a.srz, &a.skx, &a.sky, &a.skz, &a.sL, &a.sLth, &a.resA, &a.resB, &a.resS, &a.fuseU,
                        &a.fuseThr})
         take(*d, nslots);
+    // a polarised simulation: the detection records' Stokes parameters and, per slot, the packet's Stokes vector,
+    // normal and flag (52 bytes per slot); nothing otherwise, so that the other arrays lie where they did
+    a.detPol = nullptr;
+    a.sQ = a.sU = a.sV = a.snx = a.sny = a.snz = nullptr;
+    a.spol = nullptr;
+    if (pol) {
+        take(a.detPol, (detPair ? 2 : 1) * (rayCap - nslots));
+        for (double** d : {&a.sQ, &a.sU, &a.sV, &a.snx, &a.sny, &a.snz}) take(*d, nslots);
+        take(a.spol, nslots);
+    }
     for (int** d : {&a.sell, &a.snscatt, &a.sstellar, &a.sstate, &a.svcell}) take(*d, nslots);
     for (uint32_t** d : {&a.splo, &a.sphi, &a.sblock, &a.sw2, &a.sw3, &a.shave}) take(*d, nslots);
     take(a.act[0], nslots);
@@ -2161,17 +2277,19 @@ size_t poolLayout(char* base, size_t nslots, size_t rayCap, bool detPair, bool p
     return bytes;
 }
 
-int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair) {
+int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair, bool pol) {
     const int ninstr = (int)c->instr.size();
     const size_t rays = (size_t)nslots * (1 + ninstr) + (continuous ? (size_t)nslots * kPathCap * ninstr : 0);
     if (rays >= (size_t)INT32_MAX) return fail(c, SKIRT_ERR_UNSUPPORTED, "ray queue too large");
     const int rayCap = (int)rays;
     const bool path = continuous && nslots > 0;
-    if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolPath == path && c->poolDetPair == detPair)
+    if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolPath == path && c->poolDetPair == detPair &&
+        c->poolPol == pol)
         return SKIRT_OK;
     Args counted{};
-    const size_t bytes = poolLayout(nullptr, (size_t)nslots, (size_t)rayCap, detPair, path, counted) + kPoolSpare;
+    const size_t bytes = poolLayout(nullptr, (size_t)nslots, (size_t)rayCap, detPair, path, pol, counted) + kPoolSpare;
     c->poolPath = path;
+    c->poolPol = pol;
     c->poolDetPair = detPair;
     if (c->dPool) { (void)hipFree(c->dPool); c->dPool = nullptr; }
     HIPCHECK(c, hipMalloc(&c->dPool, bytes));
@@ -2182,7 +2300,7 @@ int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair) {
 }
 
 void carvePool(SkirtMcrt* c, Args& a) {
-    poolLayout(static_cast<char*>(c->dPool), (size_t)c->nslots, (size_t)c->rayCap, c->poolDetPair, c->poolPath, a);
+    poolLayout(static_cast<char*>(c->dPool), (size_t)c->nslots, (size_t)c->rayCap, c->poolDetPair, c->poolPath, c->poolPol, a);
     a.nslots = c->nslots;
     a.rayCap = c->rayCap;
     a.ctr = c->dCtr;
@@ -2296,6 +2414,16 @@ int ensureLeafMap(SkirtMcrt* c) {
 }
 
 #include "density_sample.hpp"
+
+// polProbeOne (polarization.hpp) on n packet states, one per thread (skirt_mcrt_scatterings)
+__global__ void __launch_bounds__(kBlock)
+    scatteringsKernel(const double* tab, int ncomp, int nlambda, int nt, const double* states, const double* deviates,
+                      double kox, double koy, double koz, double kyx, double kyy, double kyz, size_t n, double* out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double kobs[3] = {kox, koy, koz}, ky[3] = {kyx, kyy, kyz};
+    polProbeOne(tab, ncomp, nlambda, nt, states + polStateWords * i, deviates + 2 * i, kobs, ky, out + polResultWords * i);
+}
 
 }  // namespace
 
@@ -2710,6 +2838,15 @@ int skirt_mcrt_upload_media(SkirtMcrt* c, const SkirtMediaDesc* m) {
     if (m->nlambda >= (1 << 14)) return fail(c, SKIRT_ERR_ARG, "at most 16383 wavelengths");
     HIPCHECK(c, hipSetDevice(c->device));
     c->mapReady = false;  // the leaf map caches the densities
+    if (c->dPolTab && (m->ncomp != c->ncomp || m->nlambda != c->nlambda)) {  // Mueller tables of other media
+        // (instruments set with them keep their Stokes slots, which no unpolarised kernel fills: as set_mueller)
+        if (!c->instr.empty())
+            return fail(c, SKIRT_ERR_STATE, "media of other sizes drop the Mueller tables: clear the instruments first");
+        (void)hipFree(c->dPolTab);
+        c->dPolTab = nullptr;
+        c->polTab.clear();
+        c->polNtheta = 0;
+    }
     c->ncomp = m->ncomp;
     c->nlambda = m->nlambda;
     const size_t nt = (size_t)m->ncomp * m->nlambda;
@@ -2806,6 +2943,11 @@ int skirt_mcrt_set_instruments(SkirtMcrt* c, const SkirtInstrDesc* in, int n) {
         d.levels = d.kind == SKIRT_INSTR_FULL ? in[i].scattering_levels : 0;
         if (d.levels < 0 || d.levels > 250) return fail(c, SKIRT_ERR_ARG, "scattering levels out of range");
         d.nslots = d.kind == SKIRT_INSTR_FULL ? 5 + d.levels : 1;
+        // a polarised simulation's FullInstrument: Stokes Q, U, V after the scattering levels
+        if (d.kind == SKIRT_INSTR_FULL && c->dPolTab) {
+            d.stokes = d.nslots;
+            d.nslots += 3;
+        }
         for (int q = 0; q < 3; q++) d.kobs[q] = in[i].kobs[q];
         d.sinphi = in[i].sinphi; d.cosphi = in[i].cosphi; d.sintheta = in[i].sintheta; d.costheta = in[i].costheta;
         d.sinpa = in[i].sinpa; d.cospa = in[i].cospa;
@@ -3247,8 +3389,8 @@ static int planLds(SkirtMcrt* c, PhasePlan& pl) {
     c->lastDetCopies = a.detCopies;
     // launches above 64 KiB of dynamic LDS declare it first
     if (pl.ldsDetect > 64 * 1024)
-        HIPCHECK(c, hipFuncSetAttribute((const void*)detectKernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)pl.ldsDetect));
+        HIPCHECK(c, hipFuncSetAttribute(a.pol ? (const void*)detectKernel<true> : (const void*)detectKernel<false>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.ldsDetect));
     return SKIRT_OK;
 }
 
@@ -3282,7 +3424,8 @@ static int planPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint
     // C2 -1.5 %. Not for Voronoi grids: C4 -2.2 %, and -2.6 % again after the counter-line and event-grid
     // changes (profiles/r05_detect_aside_ab.txt)
     pl.detAside = !continuous && !c->instr.empty() && p->has_dust && c->gridKind != SKIRT_GRID_VORONOI;
-    if ((rc = ensurePool(c, slots, continuous, pl.detAside))) return rc;
+    const bool pol = c->dPolTab != nullptr && p->has_dust;  // (runPhase has refused what has no polarised kernel)
+    if ((rc = ensurePool(c, slots, continuous, pl.detAside, pol))) return rc;
     if (pl.detAside && !c->sD) {
         HIPCHECK(c, hipStreamCreateWithFlags(&c->sD, hipStreamNonBlocking));
         HIPCHECK(c, hipEventCreateWithFlags(&c->evDetT, hipEventDisableTiming));
@@ -3300,6 +3443,9 @@ static int planPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint
         a.mapX0 = c->mapOrigin[0]; a.mapY0 = c->mapOrigin[1]; a.mapZ0 = c->mapOrigin[2];
     }
     a.optics = c->dOptics;
+    a.pol = pol ? 1 : 0;
+    a.polTab = pol ? c->dPolTab : nullptr;
+    a.polNtheta = c->polNtheta;
     a.nstar = c->nstar; a.geomParam = c->dGeomParam; a.geomTable = c->dGeomTable; a.lum = c->dLum;
     a.lumtot = c->dLumtot; a.cdf = c->dCdf; a.emissionBias = c->emissionBias;
     a.ninstr = (int)c->instr.size(); a.instr = c->dInstr; a.nsed = c->nsed;
@@ -3365,8 +3511,12 @@ static int runIterations(SkirtMcrt* c, const PhasePlan& pl) {
     auto launchEvent = [&](const Args& aa, hipStream_t st) {
         withWalk(kind, [&](auto g) {
             withBool(one, [&](auto o) {
-                hipLaunchKernelGGL((eventKernel<decltype(g)::value, decltype(o)::value>), dim3(pl.egrid), dim3(kBlock),
-                                   pl.ldsEvent, st, aa);
+                if (aa.pol)
+                    hipLaunchKernelGGL((eventKernel<decltype(g)::value, decltype(o)::value, true>), dim3(pl.egrid),
+                                       dim3(kBlock), pl.ldsEvent, st, aa);
+                else
+                    hipLaunchKernelGGL((eventKernel<decltype(g)::value, decltype(o)::value>), dim3(pl.egrid), dim3(kBlock),
+                                       pl.ldsEvent, st, aa);
             });
         });
     };
@@ -3392,6 +3542,7 @@ static int runIterations(SkirtMcrt* c, const PhasePlan& pl) {
     Args aa = pl.a, prev;
     carvePool(c, aa);
     DetRec* const detBase = aa.det;
+    DetPol* const detPolBase = aa.detPol;
     int rc, its = 0, polls = 0;
     int pollIt[kPollRing] = {};  // the iteration count each copy was taken at
     bool pendingDet = false;
@@ -3408,7 +3559,8 @@ static int runIterations(SkirtMcrt* c, const PhasePlan& pl) {
             HIPCHECK(c, hipEventRecord(c->evDetT, st));
             HIPCHECK(c, hipStreamWaitEvent(sd, c->evDetT, 0));
         }
-        hipLaunchKernelGGL(detectKernel, dim3(pl.dgrid), dim3(kBlock), pl.ldsDetect, sd, d);
+        if (d.pol) hipLaunchKernelGGL(detectKernel<true>, dim3(pl.dgrid), dim3(kBlock), pl.ldsDetect, sd, d);
+        else hipLaunchKernelGGL(detectKernel<false>, dim3(pl.dgrid), dim3(kBlock), pl.ldsDetect, sd, d);
         HIPCHECK(c, hipGetLastError());
         HIPCHECK(c, hipMemsetAsync(CTRP(d.ctr, CTR_DET + d.parity), 0, sizeof(unsigned int), sd));
         if (pl.detAside) {
@@ -3445,6 +3597,7 @@ static int runIterations(SkirtMcrt* c, const PhasePlan& pl) {
             // this iteration's detection records: the region of its parity, free once the detect kernel of
             // the last iteration of that parity is done
             aa.det = detBase + (size_t)aa.parity * (size_t)(c->rayCap - c->nslots);
+            if (detPolBase) aa.detPol = detPolBase + (size_t)aa.parity * (size_t)(c->rayCap - c->nslots);
             if (detUsed[aa.parity]) HIPCHECK(c, hipStreamWaitEvent(st, c->evDet[aa.parity], 0));
         }
         if (aa.continuous && !aa.init) {  // the continuous peel-offs of the FILL rays that just returned
@@ -3486,6 +3639,12 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
     if (phase < SKIRT_PHASE_STELLAR || phase > SKIRT_PHASE_DUST_SELFABS) return fail(c, SKIRT_ERR_ARG, "unknown phase");
     if (cycle >= (1u << 30)) return fail(c, SKIRT_ERR_ARG, "cycle number too large");
     const bool cellPhase = phase != SKIRT_PHASE_STELLAR;
+    // polarised scattering: the stellar phase's interaction-point peel-offs only (the continuous peel-off and the
+    // dust phases have no polarised kernels: refused, not run unpolarised)
+    if (c->dPolTab && p->has_dust && p->continuous_scattering)
+        return fail(c, SKIRT_ERR_UNSUPPORTED, "continuous scattering is not supported with polarised dust mixes");
+    if (c->dPolTab && cellPhase)
+        return fail(c, SKIRT_ERR_UNSUPPORTED, "dust emission phases are not supported with polarised dust mixes");
     if (cellPhase && (!c->dCellLtot || !p->has_dust)) return fail(c, SKIRT_ERR_STATE, "a dust phase needs a dust system and uploaded cell sources");
     if (c->gridKind < 0 && p->has_dust) return fail(c, SKIRT_ERR_STATE, "no grid uploaded");
     if (!cellPhase && !c->dLumtot) return fail(c, SKIRT_ERR_STATE, "no sources uploaded");
@@ -3704,7 +3863,7 @@ void skirt_mcrt_destroy(SkirtMcrt* c) {
                     c->dEmisScratch, c->dDevCell, c->dSite, c->dCellBbox, c->dVorStart, c->dVorSlots,
                     c->dBlockOffset, c->dBlockSites, c->dRho,
                     c->dOptics, c->dGeomParam, c->dGeomTable, c->dLum, c->dLumtot, c->dCdf, c->dInstr,
-                    c->dClaim, c->dStats, c->dError, c->dCtr, c->dPool, c->dCrossed};
+                    c->dClaim, c->dStats, c->dError, c->dCtr, c->dPool, c->dCrossed, c->dPolTab};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (c->hCtr) (void)hipHostFree(c->hCtr);
@@ -3756,6 +3915,79 @@ int skirt_mcrt_sample_positions(SkirtMcrt* c, int comp, uint64_t seed, uint64_t 
     if (dPos) (void)hipFree(dPos);
     if (dDraws) (void)hipFree(dDraws);
     if (dErr) (void)hipFree(dErr);
+    return rc;
+}
+
+int skirt_mcrt_set_mueller(SkirtMcrt* c, const SkirtMuellerDesc* m) {
+    if (!c) return SKIRT_ERR_ARG;
+    if (!c->instr.empty()) return fail(c, SKIRT_ERR_STATE, "set_mueller after set_instruments (it changes their slots)");
+    HIPCHECK(c, hipSetDevice(c->device));
+    if (c->dPool) { (void)hipFree(c->dPool); c->dPool = nullptr; c->nslots = 0; }
+    if (!m) {  // unpolarised, as without the call
+        if (c->dPolTab) { (void)hipFree(c->dPolTab); c->dPolTab = nullptr; }
+        c->polTab.clear();
+        c->polNtheta = 0;
+        return SKIRT_OK;
+    }
+    if (c->ncomp < 1 || c->nlambda < 1) return fail(c, SKIRT_ERR_STATE, "set_mueller before upload_media");
+    if (m->ncomp != c->ncomp || m->nlambda != c->nlambda || m->ntheta < 2 || m->ntheta > 100000 || !m->S11 || !m->S12 ||
+        !m->S33 || !m->S34 || !m->thetaX || !m->pfnorm)
+        return fail(c, SKIRT_ERR_ARG, "Mueller tables do not match the media (ntheta >= 2, no null table)");
+    const size_t plane = (size_t)m->ncomp * m->nlambda * m->ntheta, rows = (size_t)m->ncomp * m->nlambda;
+    std::vector<double> tab(polTableWords(m->ncomp, m->nlambda, m->ntheta));
+    const double* src[5] = {m->S11, m->S12, m->S33, m->S34, m->thetaX};
+    for (int q = 0; q < 5; q++) std::memcpy(tab.data() + q * plane, src[q], plane * sizeof(double));
+    std::memcpy(tab.data() + 5 * plane, m->pfnorm, rows * sizeof(double));
+    double* phi = tab.data() + 5 * plane + rows;
+    polPhiTables(nullptr, phi, phi + polNphi, phi + 2 * polNphi);
+    const int rc = upload(c, c->dPolTab, tab.data(), tab.size());
+    if (rc) return rc;
+    c->polTab.swap(tab);
+    c->polNtheta = m->ntheta;
+    return SKIRT_OK;
+}
+
+int skirt_mcrt_scatterings(SkirtMcrt* c, int instrument, size_t n, const double* states, const double* deviates,
+                           double* out) {
+    if (!c) return SKIRT_ERR_ARG;
+    if (!c->dPolTab) return fail(c, SKIRT_ERR_STATE, "scatterings before set_mueller");
+    if (instrument < 0 || instrument >= (int)c->instr.size() || (n && (!states || !deviates || !out)))
+        return fail(c, SKIRT_ERR_ARG, "bad instrument or buffer");
+    for (size_t i = 0; i < n; i++) {
+        const double ell = states[polStateWords * i + 10], h = states[polStateWords * i + 11];
+        if (!(ell >= 0 && ell < c->nlambda && h >= 0 && h < c->ncomp && ell == (int)ell && h == (int)h))
+            return fail(c, SKIRT_ERR_ARG, "a state's wavelength or component index is out of range");
+    }
+    if (n == 0) return SKIRT_OK;
+    const size_t nblocks = (n + kBlock - 1) / kBlock;
+    if (nblocks > 0x7fffffffu) return fail(c, SKIRT_ERR_ARG, "too many states");
+    HIPCHECK(c, hipSetDevice(c->device));
+    const DevInstr& ins = c->instr[instrument];
+    // DistantInstrument::bfky, as Events::peelWeightPol
+    const double kyx = -ins.cosphi * ins.costheta * ins.cospa - ins.sinphi * ins.sinpa;
+    const double kyy = -ins.sinphi * ins.costheta * ins.cospa + ins.cosphi * ins.sinpa;
+    const double kyz = +ins.sintheta * ins.cospa;
+    const size_t nin = polStateWords * n, ndv = 2 * n, nout = polResultWords * n;
+    double* buf = nullptr;
+    int rc = SKIRT_OK;
+    if (hipMalloc(&buf, (nin + ndv + nout) * sizeof(double)) != hipSuccess) {
+        rc = fail(c, SKIRT_ERR_HIP, "scatterings: allocation failed");
+    } else if (hipMemcpyAsync(buf, states, nin * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+               hipMemcpyAsync(buf + nin, deviates, ndv * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        rc = fail(c, SKIRT_ERR_HIP, "scatterings: a copy failed");
+    } else {
+        hipLaunchKernelGGL(scatteringsKernel, dim3((unsigned)nblocks), dim3(kBlock), 0, c->stream, c->dPolTab, c->ncomp,
+                           c->nlambda, c->polNtheta, buf, buf + nin, ins.kobs[0], ins.kobs[1], ins.kobs[2], kyx, kyy, kyz, n,
+                           buf + nin + ndv);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(out, buf + nin + ndv, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess)
+            rc = fail(c, SKIRT_ERR_HIP, "scatterings: the kernel or a copy failed");
+    }
+    if (buf) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(buf);
+    }
     return rc;
 }
 

@@ -876,6 +876,32 @@ void finishMix(DustMix& mix, const std::vector<double>& muv, const std::vector<s
     }
 }
 
+// What DustMix::setupSelfAfter derives from a polarising mix's Mueller tables (DustMix.cpp:96-123), in its
+// operations and order: the normalized cumulative distribution of theta (NR::cdf over S11(t+1) sin theta(t+1) dt)
+// and the phase function normalization per wavelength. (The phi tables, the same for every mix, are the engine's:
+// device/polarization.hpp polPhiTables.)
+void finishPolarization(DustMix& mix, int Nlambda) {
+    const int Ntheta = mix.ntheta;
+    std::vector<double> thetav(Ntheta);
+    const double dt = M_PI / (Ntheta - 1);
+    for (int t = 0; t < Ntheta; t++) thetav[t] = t * dt;
+    mix.thetaX.assign((size_t)Nlambda * Ntheta, 0.0);
+    mix.pfnorm.assign(Nlambda, 0.0);
+    for (int ell = 0; ell < Nlambda; ell++) {
+        const double* S11 = &mix.S11[(size_t)ell * Ntheta];
+        double* Pv = &mix.thetaX[(size_t)ell * Ntheta];
+        for (int i = 0; i < Ntheta - 1; i++) Pv[i + 1] = Pv[i] + S11[i + 1] * sin(thetav[i + 1]) * dt;
+        const double norm = Pv[Ntheta - 1];
+        for (int i = 0; i < Ntheta; i++) Pv[i] /= norm;
+    }
+    for (int ell = 0; ell < Nlambda; ell++) {
+        const double* S11 = &mix.S11[(size_t)ell * Ntheta];
+        double sum = 0.;
+        for (int t = 0; t < Ntheta; t++) sum += S11[t] * sin(thetav[t]) * dt;
+        mix.pfnorm[ell] = 2.0 / sum;
+    }
+}
+
 DustMix parseMix(const Ctx& c, const XmlElement* e, const WavelengthGrid& wl) {
     DustMix mix;
     mix.type = e->name;
@@ -950,10 +976,36 @@ DustMix parseMix(const Ctx& c, const XmlElement* e, const WavelengthGrid& wl) {
         sabs.push_back(nr::resample<nr::interpolateLogLog>(wl.lambda, lambdav, sabsv));
         ssca.push_back(nr::resample<nr::interpolateLogLog>(wl.lambda, lambdav, sscav));
         gv.push_back(nr::resample<nr::interpolateLogLin>(wl.lambda, lambdav, gvv));
+    } else if (e->name == "ElectronDustMix") {
+        // ElectronDustMix.cpp setupSelfBefore: Thomson scattering, no absorption, one population of electrons, and
+        // the Mueller matrix of equation (C.7) of Wolf 2003 at 181 angles, the same at every wavelength
+        const int Ntheta = 181;
+        std::vector<double> zero(Nlambda, 0.0), sigmasca(Nlambda, constants::sigmaThomson);
+        mix.polarization = true;
+        mix.ntheta = Ntheta;
+        for (std::vector<double>* S : {&mix.S11, &mix.S12, &mix.S33, &mix.S34}) S->assign((size_t)Nlambda * Ntheta, 0.0);
+        const double dt = M_PI / (Ntheta - 1);
+        for (int t = 0; t < Ntheta; t++) {
+            const double theta = t * dt;
+            const double costheta = cos(theta);
+            const double S11 = 0.5 * (costheta * costheta + 1.);
+            const double S12 = 0.5 * (costheta * costheta - 1.);
+            const double S33 = costheta;
+            for (int ell = 0; ell < Nlambda; ell++) {
+                mix.S11[(size_t)ell * Ntheta + t] = S11;
+                mix.S12[(size_t)ell * Ntheta + t] = S12;
+                mix.S33[(size_t)ell * Ntheta + t] = S33;
+            }
+        }
+        muv.push_back(constants::melectron);
+        sabs.push_back(zero);
+        ssca.push_back(sigmasca);
+        gv.push_back(zero);
     } else {
         throw std::runtime_error("unsupported dust mix " + e->name);
     }
     finishMix(mix, muv, sabs, ssca, gv, Nlambda);
+    if (mix.polarization) finishPolarization(mix, Nlambda);
     return mix;
 }
 
@@ -1750,6 +1802,19 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
             m.dust.push_back(comp);
         }
         if (m.dust.empty()) throw std::runtime_error("dust distribution has no components");
+        // DustSystem::setupSelfBefore (DustSystem.cpp:71-75), in the reference's words
+        for (const DustComp& comp : m.dust)
+            if (comp.mix.polarization != m.dust[0].mix.polarization)
+                throw std::runtime_error("All dust mixes must consistenly support polarization, or not support polarization");
+        m.polarization = m.dust[0].mix.polarization;
+        for (const DustComp& comp : m.dust)  // (the engine's tables are [component][wavelength][angle])
+            if (m.polarization && comp.mix.ntheta != m.dust[0].mix.ntheta)
+                throw std::runtime_error("polarised dust mixes with different numbers of scattering angles are not supported");
+        // beyond the engine's polarised kernels (MonteCarloSimulation.cpp:420-428; the dust emission phases)
+        if (m.polarization && m.continuousScattering)
+            throw std::runtime_error("continuous scattering is not supported with polarised dust mixes (ElectronDustMix)");
+        if (m.polarization && m.dustEmission)
+            throw std::runtime_error("dust emission is not supported with polarised dust mixes (ElectronDustMix)");
 
         const XmlElement* ge = need(ds, "dustGrid");
         if (ge->name == "CartesianDustGrid") {
@@ -2004,6 +2069,8 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
     // ---- instruments
     if (const XmlElement* is = sim->item("instrumentSystem"))
         for (const XmlElement* ie : is->items("instruments")) m.instruments.push_back(parseInstrument(c, ie));
+    // FullInstrument::setupSelfBefore (FullInstrument.cpp:51-54, 79-87): Stokes arrays with a polarising dust system
+    for (Instrument& ins : m.instruments) ins.polarization = ins.kind == InstrumentKind::Full && m.hasDust && m.polarization;
     return m;
 }
 

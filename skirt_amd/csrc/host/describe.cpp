@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../../include/skirt_host.h"
+#include "../device/polarization.hpp"
 
 namespace {
 
@@ -120,7 +121,36 @@ void writeInstruments(Writer& w, const SkirtInstrDesc* d, int n) {
     }
 }
 
+void writeMueller(Writer& w, const SkirtMuellerDesc& m) {
+    const size_t rows = (size_t)m.ncomp * m.nlambda, t = rows * m.ntheta;
+    w.i1("mueller.ncomp", m.ncomp);
+    w.i1("mueller.nlambda", m.nlambda);
+    w.i1("mueller.ntheta", m.ntheta);
+    w.d("mueller.S11", m.S11, t);
+    w.d("mueller.S12", m.S12, t);
+    w.d("mueller.S33", m.S33, t);
+    w.d("mueller.S34", m.S34, t);
+    w.d("mueller.thetaX", m.thetaX, t);
+    w.d("mueller.pfnorm", m.pfnorm, rows);
+    // the phi tables every mix shares (DustMix.cpp:125-139), as the engine builds them
+    double phi[4][polNphi];
+    polPhiTables(phi[0], phi[1], phi[2], phi[3]);
+    w.d("mueller.phi", phi[0], polNphi);
+    w.d("mueller.phi1", phi[1], polNphi);
+    w.d("mueller.phis", phi[2], polNphi);
+    w.d("mueller.phic", phi[3], polNphi);
+}
+
 }  // namespace
+
+extern "C" int skirt_host_write_mueller(const char* path, const SkirtMuellerDesc* mueller) {
+    if (!path || !mueller) return SKIRT_ERR_ARG;
+    FILE* f = std::fopen(path, "ab");
+    if (!f) return SKIRT_ERR_ARG;
+    Writer w{f};
+    writeMueller(w, *mueller);
+    return std::fclose(f) == 0 ? SKIRT_OK : SKIRT_ERR_ARG;
+}
 
 extern "C" int skirt_host_write_descriptors(const char* path, const SkirtGridDesc* grid, const SkirtMediaDesc* media,
                                             const SkirtSourceDesc* sources, const SkirtInstrDesc* instr, int ninstr) {

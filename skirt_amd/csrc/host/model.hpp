@@ -248,6 +248,13 @@ struct DustMix {
     // per-population cross sections (needed for dust emission equilibrium temperatures)
     double mu = 0;
     std::vector<double> sigmaabs;  // per ell, summed over populations
+    // a mix that supports polarisation (DustMix::addpolarization; ElectronDustMix.cpp): the Mueller matrix elements
+    // at ntheta scattering angles per wavelength, [ell][t] row-major, and what DustMix::setupSelfAfter derives from
+    // them (DustMix.cpp:96-123): the cumulative distribution of theta and the phase function's normalization
+    bool polarization = false;
+    int ntheta = 0;
+    std::vector<double> S11, S12, S33, S34, thetaX;
+    std::vector<double> pfnorm;  // per ell
 };
 
 struct DustComp {
@@ -349,6 +356,8 @@ struct Instrument {
     int Nx = 250, Ny = 250;
     double fovx = 0, fovy = 0, xc = 0, yc = 0;
     int scatteringLevels = 0;
+    // FullInstrument::_polarization: the dust system's mixes polarise, so the instrument has Stokes Q, U, V arrays
+    bool polarization = false;
     // derived
     double costheta = 1, sintheta = 0, cosphi = 1, sinphi = 0, cospa = 1, sinpa = 0;
     double kobs[3] = {0, 0, 1}, kx[3] = {0, 0, 0}, ky[3] = {0, 0, 0};
@@ -357,7 +366,9 @@ struct Instrument {
     bool hasFrames() const { return kind != InstrumentKind::SED; }
     bool hasSeds() const { return kind != InstrumentKind::Frame; }
     // number of accumulation slots (frames and SEDs share the slot index)
-    int nslots() const { return kind == InstrumentKind::Full ? SlotLevel0 + scatteringLevels : 1; }
+    // (the Stokes Q, U, V slots of a polarised simulation follow the scattering levels)
+    int nslots() const { return kind == InstrumentKind::Full ? SlotLevel0 + scatteringLevels + (polarization ? 3 : 0) : 1; }
+    int stokesSlot() const { return SlotLevel0 + scatteringLevels; }
     int pixel(double x, double y, double z) const;
 };
 
@@ -385,6 +396,7 @@ struct Model {
 
     // dust system
     bool hasDust = false;
+    bool polarization = false;  // DustSystem::polarization(): every dust mix supports polarisation
     std::vector<DustComp> dust;
     DustGrid grid;
     std::vector<double> rho;     // Ncells x Ncomp row-major (DustSystem::_rhovv)

@@ -193,6 +193,15 @@ void writeOutputs(const Model& m, const std::string& prefix, const std::vector<s
             fnames = {"total", "direct", "scattered", "dust", "dustscattered", "transparent"};
             Fnames = {"total flux", "direct stellar flux", "scattered stellar flux", "total dust emission flux",
                       "dust emission scattered flux", "transparent flux"};
+            if (ins.polarization) {  // FullInstrument.cpp:213-219
+                const char* stokes[3] = {"Q", "U", "V"};
+                for (int q = 0; q < 3; q++) {
+                    farr.push_back(fslot(ins.stokesSlot() + q));
+                    Farr.push_back(Fslot(ins.stokesSlot() + q));
+                    fnames.push_back(std::string("stokes") + stokes[q]);
+                    Fnames.push_back(std::string("total Stokes ") + stokes[q]);
+                }
+            }
             for (int n = 0; n < ins.scatteringLevels; n++) {
                 farr.push_back(fslot(SlotLevel0 + n));
                 Farr.push_back(Fslot(SlotLevel0 + n));

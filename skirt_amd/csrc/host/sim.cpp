@@ -15,6 +15,7 @@
 #include "model.hpp"
 #include "outputs.hpp"
 #include "../device/philox.hpp"
+#include "../device/polarization.hpp"
 
 using namespace skirt;
 
@@ -30,6 +31,7 @@ struct SkirtSim {
     double setupSeconds = 0;
     uint64_t npp = 0;
     SkirtMcrt* eng = nullptr;
+    int device = -1;                          // the HIP device of eng (skirt_sim_attach)
     std::vector<double> labs;                 // Ncells x Nlambda (stellar)
     std::vector<double> labsDust;             // Ncells x Nlambda (last self-absorption cycle)
     bool dustLabsOnDevice = false;            // labsDust is still to be downloaded (skirt_sim_fetch)
@@ -252,6 +254,10 @@ struct Descs {
     std::vector<SkirtInstrDesc> ids;
     std::vector<double> kext, ksca, alb, gg, gp, lum, cdf, gt;
     std::vector<int> gk;
+    // a polarising model's Mueller tables, [comp][ell][theta]
+    bool hasMueller = false;
+    SkirtMuellerDesc mu{};
+    std::vector<double> S11, S12, S33, S34, thetaX, pfnorm;
 };
 
 void buildDescs(const Model& m, Descs& d) {
@@ -314,6 +320,21 @@ void buildDescs(const Model& m, Descs& d) {
                 d.gg[h * Nl + ell] = m.dust[h].mix.g[ell];
             }
         d.md = SkirtMediaDesc{m.ncells(), nc, Nl, m.rho.data(), d.kext.data(), d.ksca.data(), d.alb.data(), d.gg.data()};
+        if (m.polarization) {
+            d.hasMueller = true;
+            const int nt = m.dust[0].mix.ntheta;  // (the same for every mix: loadSki checks)
+            for (int h = 0; h < nc; h++) {
+                const DustMix& x = m.dust[h].mix;
+                d.S11.insert(d.S11.end(), x.S11.begin(), x.S11.end());
+                d.S12.insert(d.S12.end(), x.S12.begin(), x.S12.end());
+                d.S33.insert(d.S33.end(), x.S33.begin(), x.S33.end());
+                d.S34.insert(d.S34.end(), x.S34.begin(), x.S34.end());
+                d.thetaX.insert(d.thetaX.end(), x.thetaX.begin(), x.thetaX.end());
+                d.pfnorm.insert(d.pfnorm.end(), x.pfnorm.begin(), x.pfnorm.end());
+            }
+            d.mu = SkirtMuellerDesc{nc, Nl, nt, d.S11.data(), d.S12.data(), d.S33.data(), d.S34.data(), d.thetaX.data(),
+                                    d.pfnorm.data()};
+        }
     }
     const int ns = (int)m.starL.size();
     d.gk.assign(ns, SKIRT_GEOM_PLUMMER);
@@ -361,12 +382,14 @@ int skirt_sim_attach(SkirtSim* s, int device) {
     if (s->eng) { skirt_mcrt_destroy(s->eng); s->eng = nullptr; }
     int rc = skirt_mcrt_create(device, &s->eng);
     if (rc) { g_err = "cannot create the engine on device " + std::to_string(device); return rc; }
+    s->device = device;
     const Model& m = s->m;
     Descs d;
     buildDescs(m, d);
     if (d.hasGrid) {
         if ((rc = check(s, skirt_mcrt_upload_grid(s->eng, &d.g)))) return rc;
         if ((rc = check(s, skirt_mcrt_upload_media(s->eng, &d.md)))) return rc;
+        if (d.hasMueller && (rc = check(s, skirt_mcrt_set_mueller(s->eng, &d.mu)))) return rc;
     }
     if ((rc = check(s, skirt_mcrt_upload_sources(s->eng, &d.sd)))) return rc;
     if ((rc = check(s, skirt_mcrt_set_instruments(s->eng, d.ids.data(), (int)d.ids.size())))) return rc;
@@ -387,8 +410,51 @@ int skirt_sim_describe(SkirtSim* s, const char* path) {
     else { g_err = std::string("cannot write ") + path; return SKIRT_ERR_ARG; }
     int rc = skirt_host_write_descriptors(path, d.hasGrid ? &d.g : nullptr, d.hasGrid ? &d.md : nullptr, &d.sd,
                                           d.ids.data(), (int)d.ids.size());
+    if (!rc && d.hasMueller) rc = skirt_host_write_mueller(path, &d.mu);
     if (rc) g_err = std::string("cannot write ") + path;
     return rc;
+}
+
+int skirt_sim_polarization(SkirtSim* s) { return s && s->m.hasDust && s->m.polarization ? 1 : 0; }
+
+int skirt_sim_scatterings(SkirtSim* s, int instrument, int device, size_t n, const double* states, const double* deviates,
+                          double* out) {
+    if (!s || (n && (!states || !deviates || !out))) return SKIRT_ERR_ARG;
+    if (!skirt_sim_polarization(s)) { g_err = "the simulation's dust mixes do not polarise"; return SKIRT_ERR_STATE; }
+    if (instrument < 0 || instrument >= (int)s->m.instruments.size()) {
+        g_err = "no instrument " + std::to_string(instrument);
+        return SKIRT_ERR_ARG;
+    }
+    if (device >= 0) {
+        if (!s->eng) { g_err = "no engine attached"; return SKIRT_ERR_STATE; }
+        if (device != s->device) {
+            g_err = "the engine is attached to device " + std::to_string(s->device) + ", not " + std::to_string(device);
+            return SKIRT_ERR_ARG;
+        }
+        return check(s, skirt_mcrt_scatterings(s->eng, instrument, n, states, deviates, out));
+    }
+    // the host's compilation of the engine's routines, on the tables as the engine lays them out
+    Descs d;
+    buildDescs(s->m, d);
+    const int nc = d.mu.ncomp, nl = d.mu.nlambda, nt = d.mu.ntheta;
+    const size_t plane = (size_t)nc * nl * nt, rows = (size_t)nc * nl;
+    std::vector<double> tab(polTableWords(nc, nl, nt));
+    const double* src[5] = {d.mu.S11, d.mu.S12, d.mu.S33, d.mu.S34, d.mu.thetaX};
+    for (int q = 0; q < 5; q++) std::copy(src[q], src[q] + plane, tab.begin() + q * plane);
+    std::copy(d.mu.pfnorm, d.mu.pfnorm + rows, tab.begin() + 5 * plane);
+    double* phi = tab.data() + 5 * plane + rows;
+    polPhiTables(nullptr, phi, phi + polNphi, phi + 2 * polNphi);
+    const Instrument& ins = s->m.instruments[instrument];
+    for (size_t i = 0; i < n; i++) {
+        const double ell = states[polStateWords * i + 10], h = states[polStateWords * i + 11];
+        if (!(ell >= 0 && ell < nl && h >= 0 && h < nc && ell == (int)ell && h == (int)h)) {
+            g_err = "a state's wavelength or component index is out of range";
+            return SKIRT_ERR_ARG;
+        }
+        polProbeOne(tab.data(), nc, nl, nt, states + polStateWords * i, deviates + 2 * i, ins.kobs, ins.ky,
+                    out + polResultWords * i);
+    }
+    return SKIRT_OK;
 }
 
 SkirtMcrt* skirt_sim_engine(SkirtSim* s) { return s ? s->eng : nullptr; }

@@ -22,6 +22,8 @@ constexpr double pc = 3.08567758e16;
 constexpr double Msun = 1.9891e30;
 constexpr double Lsun = 3.839e26;
 constexpr double mproton = 1.67262178e-27;  // Units.cpp _Mproton
+constexpr double melectron = 9.10938215e-31;      // Units.cpp _Melectron
+constexpr double sigmaThomson = 6.652458734e-29;  // Units.cpp _sigmaThomson
 constexpr double lambdaV = 550e-9;
 constexpr double kappaV = 2600.;
 }  // namespace constants
