@@ -118,12 +118,32 @@ enum State : int { S_NEW = 0, S_FILL = 2, S_WALK = 3 };
 // peel-off categories (which FullInstrument arrays a detection adds to, FullInstrument.cpp:115-171)
 enum PeelCat : unsigned { CAT_STAR_DIRECT = 0, CAT_STAR_SCATTERED = 1, CAT_DUST_DIRECT = 2, CAT_DUST_SCATTERED = 3 };
 
-// one queued ray, 80 bytes = 5 x 16-byte chunks, written by the event kernel. The trace kernel enters the
-// grid when it pulls the ray (the path before the grid, the first cell): that lookup then overlaps with the
-// other lanes' steps instead of stalling the event kernel, whose waves are few (2 per SIMD) and long.
-// Voronoi rays are entered by the event kernel (kEnterInEvent): s0 then holds the path length before the
-// grid, ci/cj the first cell. The reciprocal direction is recomputed by the trace kernel (three divisions
-// per ray, against 24 bytes more per record written and read).
+// One queued ray, written by the event kernel (or the continuous peel-off kernel) and pulled by the trace
+// kernel, which enters the grid when it pulls the ray (the path before the grid, the first cell): that lookup
+// then overlaps with the other lanes' steps instead of stalling the event kernel, whose waves are few and long.
+// The reciprocal direction is computed by the trace kernel (three divisions per ray).
+//
+// The queue has two formats, chosen per phase (rayRefs below):
+//
+// RayRef, 16 bytes, one store: every grid the trace kernel enters itself, without continuous scattering. A ray
+// starts where its slot's packet is, and the event kernel stores that state (Events::store) in the same visit,
+// untouched until the slot's next visit; so the record only names the slot and the trace lane reads the rest
+// there (Tracer::load): the origin from srx/sry/srz[slot]; a FILL/WALK direction from skx/sky/skz[slot], a
+// peel-off's from its instrument (Args::instr, kobs); a FILL ray's luminosity from sL[slot], its fused deviate
+// and threshold from fuseU/fuseThr[slot]; a queued WALK ray's optical depth from fuseU[slot] (the FILL that
+// used it is over). A peel-off's luminosity lives in its detection record only. Against the 80-byte record
+// this takes 2 x 64 bytes per slot visit off the event kernel's stores, written at a 160-byte lane stride.
+//
+// RayRec, 80 bytes = 5 x 16-byte chunks: Voronoi grids, whose rays the event kernel enters (kEnterInEvent: s0
+// then holds the path length before the grid, ci/cj the first cell, per ray, peel-offs included), and
+// continuous scattering, whose peel-offs start at points of the path and not where the packet is.
+struct __attribute__((aligned(16))) RayRef {
+    int idx;               // FILL/WALK: slot; PEEL: detection record
+    unsigned flags;        // as RayRec::flags
+    int slot;              // the packet's slot, for all three modes
+    int spare;
+};
+static_assert(sizeof(RayRef) == 16, "ray reference layout");
 struct __attribute__((aligned(16))) RayRec {
     double x, y, z;        // c0-c1: start point
     double dx, dy, dz;     // c1-c2: direction
@@ -151,6 +171,10 @@ static_assert(GEOMS_SHELL == SKIRT_GEOM_SHELL && GEOMS_GAMMA == SKIRT_GEOM_GAMMA
               "geom_sample.hpp follows the kinds of skirt_mcrt.h");
 template <int GRID>
 constexpr bool kEnterInEvent = GRID == SKIRT_GRID_VORONOI;
+// the queue's format (RayRef or RayRec): CONT is the trace kernels' template argument; in the event kernel,
+// which serves both, Args::continuous (wave-uniform)
+template <int GRID, bool CONT>
+constexpr bool kRayRefs = !kEnterInEvent<GRID> && !CONT;
 // Voronoi cellIndex: block-list candidates loaded per round trip. Round 3 chose 4; with the round-4
 // registers 2 lets the Voronoi event kernel run 3 waves/SIMD (165 VGPRs): event 2.59 -> 2.26 ms, C4
 // 1.0225e8 -> 1.0345e8 (8: 1.021e8), profiles/r04_cellindex_group.txt
@@ -419,12 +443,11 @@ struct Args {
     // on to it along its own record. Per slot: WALK -> distance, now in resS (resA keeps tau for the event
     // kernel's own draws) | a FILL ray whose lane did not walk -> -1
     double* resS;
-    // the lane's deviate u (negative: X < xi was drawn before it) and termination threshold: they travel in the
-    // record's ci, cj and s0, which only rays entered by the event kernel (Voronoi) use; those rays find them
-    // here, per slot
+    // the lane's deviate u (negative: X < xi was drawn before it) and termination threshold, per slot. With
+    // RayRef records fuseU[slot] also holds the optical depth a queued WALK ray has to reach
     double *fuseU, *fuseThr;
     int fuse;                    // 0: FILL and WALK rays queued apart | 1: fused | 2: fused, odd slots fall back (tests)
-    RayRec* rays;
+    RayRec* rays;                // the ray queue: rayCap RayRec, or rayCap RayRef (kRayRefs) in the same place
     DetRec* det;                 // detection records of the peel-off rays
     int* act[2];                 // active slot lists (double buffered)
     unsigned long long* claim;   // next packet index (relative to first)
@@ -794,12 +817,38 @@ struct Tracer {
     // it, m = -1) and the first cell (DustGrid::path); an empty path finishes the ray at once.
     // walkOn: the lane's own fused FILL record again, now as the WALK ray to the optical depth in fillU
     __device__ __forceinline__ void load(Ray& r, unsigned id, bool walkOn) {
-        const double2* c = reinterpret_cast<const double2*>(a.rays + id);
-        const double2 c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
-        const int4 c6 = reinterpret_cast<const int4*>(c)[4];
+        double2 c3;  // RayRec: s0, param | RayRef: the slot's fuseThr, and sL (FILL) or fuseU (WALK)
+        int4 c6;     // RayRec: idx, flags, ci, cj | RayRef: idx, flags, and the slot's fuseU in z, w
         r.id = id;
-        r.x = c0.x; r.y = c0.y; r.z = c1.x;
-        r.dx = c1.y; r.dy = c2.x; r.dz = c2.y;
+        if constexpr (kRayRefs<GRID, CONT>) {
+            // the reference, then one batch of loads through its slot for every mode: the origin, the direction
+            // (the packet's, or a peel-off's instrument's) and the slot's L, deviate and threshold, which a
+            // peel-off loads and does not use (an empty path's reference names its slot as well)
+            const int4 q = reinterpret_cast<const int4*>(a.rays)[id];
+            const int slot = q.z;
+            unsigned flags = (unsigned)q.y;
+            if (kFuse && walkOn) flags = (flags & ~3u) | RAY_WALK;
+            const bool peel = rayMode(flags) == RAY_PEEL;
+            const double* kobs = a.instr[peel ? rayInstr(flags) : 0].kobs;  // (an address only, unless a peel-off)
+            const double* const px = peel ? kobs : a.skx + slot;
+            const double* const py = peel ? kobs + 1 : a.sky + slot;
+            const double* const pz = peel ? kobs + 2 : a.skz + slot;
+            r.x = a.srx[slot]; r.y = a.sry[slot]; r.z = a.srz[slot];
+            r.dx = *px; r.dy = *py; r.dz = *pz;
+            double L = a.sL[slot], u = a.fuseU[slot], thr = a.fuseThr[slot];
+            // (the values are wanted here: left alone, the compiler moves these three loads behind the mode's
+            // branches below, a second round trip for the FILL lanes)
+            asm volatile("" : "+v"(L), "+v"(u), "+v"(thr));
+            c3 = make_double2(thr, rayMode(flags) == RAY_WALK ? u : L);
+            c6 = make_int4(q.x, (int)flags, __double2loint(u), __double2hiint(u));
+        } else {
+            const double2* c = reinterpret_cast<const double2*>(a.rays + id);
+            const double2 c0 = c[0], c1 = c[1], c2 = c[2];
+            c3 = c[3];
+            c6 = reinterpret_cast<const int4*>(c)[4];
+            r.x = c0.x; r.y = c0.y; r.z = c1.x;
+            r.dx = c1.y; r.dy = c2.x; r.dz = c2.y;
+        }
         // 1/direction, 0 where |k| <= 1e-15 (that axis is never crossed), as the event kernel computed it
         r.ix = (fabs(r.dx) > 1e-15) ? 1.0 / r.dx : 0.0;
         r.iy = (fabs(r.dy) > 1e-15) ? 1.0 / r.dy : 0.0;
@@ -819,8 +868,8 @@ struct Tracer {
         if (r.mode == RAY_FILL)
             printf("E L %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", r.ell, r.x, r.y, r.z, r.dx, r.dy, r.dz, r.param);
 #endif
-        // the path before the grid of a ray the event kernel entered; the other records' s0, ci, cj are free
-        // for a fused FILL ray's threshold and deviate
+        // the path before the grid of a ray the event kernel entered (a fused FILL ray's threshold and deviate
+        // come per slot: loaded below for those rays, above with a reference's other loads)
         r.s = kEnterInEvent<GRID> ? c3.x : 0.0;
         r.kext = sh.kext[r.ell];
         // FILL: f1 = exp(-tau) = 1, f2 = scattered luminosity; WALK: tau and s at the last segment end
@@ -1078,9 +1127,30 @@ struct Events {
     // queues ray `pos`. The trace kernel enters the grid, except for Voronoi grids (kEnterInEvent): their
     // cellIndex loops over a block's site list, which costs the trace kernel more than it costs here. A
     // path found empty here (no dust system, or a Voronoi ray missing the grid) is finished here.
-    // Returns whether a ray was queued.
+    // whether the queue holds references (kRayRefs): wave-uniform; known at compile time in the polarised
+    // kernels, which have no continuous scattering (and no registers for both formats)
+    __device__ __forceinline__ bool rayRefs() const { return !kEnterInEvent<GRID> && (POL || !a.continuous); }
+
+    // Returns whether a ray was queued. Where the queue holds references (kRayRefs), the record is
+    // {idx, flags, slot}: the trace lane finds the origin, the direction and prm through the slot, whose state
+    // this visit stores (the event kernel; the continuous peel-off kernel always queues whole records)
     __device__ __forceinline__ bool emitRay(unsigned pos, const Packet& p, double dx, double dy, double dz, double prm,
-                                            int idx, unsigned flags, int& vcell) {
+                                            int idx, unsigned flags, int& vcell, int slot) {
+        if (rayRefs()) {
+            int4* const ref = reinterpret_cast<int4*>(a.rays) + pos;
+            const unsigned mode = rayMode(flags);
+            if (!a.hasDust) {  // (an empty path, as below)
+                if (mode != RAY_PEEL) {
+                    a.resA[idx] = 0.0;
+                    if (mode == RAY_WALK && a.fuse) a.resS[idx] = 0.0;
+                    if (!ONECOMP) a.resB[idx] = 0.0;
+                }
+                *ref = make_int4(idx, (int)RAY_NONE, slot, 0);
+                return false;
+            }
+            *ref = make_int4(idx, (int)flags, slot, 0);
+            return true;
+        }
         Ray r;
         r.x = p.rx; r.y = p.ry; r.z = p.rz;
         r.dx = dx; r.dy = dy; r.dz = dz;
@@ -1137,11 +1207,14 @@ struct Events {
             p.sv.pol = a.spol[s];
         }
     }
-    __device__ __forceinline__ void store(int s, const Packet& p) const {
+    // fresh: the slot launched a packet in this visit; its wavelength, its origin (star or dust) and its
+    // termination threshold change at no other time
+    __device__ __forceinline__ void store(int s, const Packet& p, bool fresh) const {
         a.srx[s] = p.rx; a.sry[s] = p.ry; a.srz[s] = p.rz;
         a.skx[s] = p.kx; a.sky[s] = p.ky; a.skz[s] = p.kz;
-        a.sL[s] = p.L; a.sLth[s] = p.Lth;
-        a.sell[s] = p.ell; a.snscatt[s] = p.nscatt; a.sstellar[s] = p.stellar; a.sstate[s] = p.state;
+        a.sL[s] = p.L;
+        if (fresh) { a.sLth[s] = p.Lth; a.sell[s] = p.ell; a.sstellar[s] = p.stellar; }
+        a.snscatt[s] = p.nscatt; a.sstate[s] = p.state;
         a.splo[s] = p.rng.plo; a.sphi[s] = p.rng.phi; a.sblock[s] = p.rng.block;
         a.sw2[s] = p.rng.w2; a.sw3[s] = p.rng.w3; a.shave[s] = p.rng.have;
         if constexpr (POL) {
@@ -1734,6 +1807,7 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, PO
         }
         // slots without a packet claim the next global packet indices (one atomic per block)
         bool need = valid && p.state == S_NEW && mainMode == RAY_NONE;
+        bool fresh = false;  // the slot launches a packet in this visit (Events::store)
         while (__syncthreads_or(need)) {
             unsigned long long* const ctrs[1] = {a.claim};
             const unsigned long long cnt[1] = {need ? 1ull : 0ull};
@@ -1744,6 +1818,7 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, PO
                 if (idx >= total) need = false;  // exhausted: the slot retires
                 else if (E.launch(p, globalPacket(a, a.first + idx))) {
                     vcell = kNoCell;  // a new position
+                    fresh = true;
                     if constexpr (POL) polSetUnpolarized(p.sv);  // PhotonPackage::launch
                     if (!(p.L > 0) && !a.crossed) {
                         // a zero-weight dust packet (a cell without emission drawn uniformly): every
@@ -1848,32 +1923,27 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, PO
                 flags = mainMode | ((unsigned)p.ell << 18);
                 at = back ? (unsigned)a.rayCap - 1u - wpos : pos++;
             }
-            const bool in = E.emitRay(at, p, dx, dy, dz, prm, idx, flags, vcell);  // (one call site: one inlined grid entry)
+            const bool in = E.emitRay(at, p, dx, dy, dz, prm, idx, flags, vcell, slot);  // (one call site: one inlined grid entry)
             if (k >= npeel && in && mainMode == RAY_FILL) fillAt = (int)at;
         }
         // the slot stays active while it has a FILL/WALK ray in flight
         if (active) actOut[apos] = slot;
-        if (valid) E.store(slot, p);
+        if (valid) E.store(slot, p, fresh);
+        // a queued WALK ray's optical depth, where the queue holds references (kRayRefs): the slot's FILL ray,
+        // whose deviate lay there, is over
+        if (E.rayRefs() && mainMode == RAY_WALK) a.fuseU[slot] = mainParam;
         if (kEnterInEvent<GRID> && valid) a.svcell[slot] = vcell;
         // A fused FILL ray: its lane gets the deviates that this packet's next visit will draw (from a copy
         // of the counter-based stream: the packet's own does not advance; X < xi as the sign of u) and that
-        // visit's termination threshold (decideFill). Added to the queued record here, where the round
-        // holds little else in registers: in its s0, ci and cj, which only a ray entered by the event
-        // kernel uses (those find them per slot)
+        // visit's termination threshold (decideFill). Written per slot here, where the round holds little else
+        // in registers; the lane finds them through the ray's slot, whatever the queue's format
         if (a.fuse && fillAt >= 0) {
             PacketRng ahead = p.rng;
             const bool biased = a.xi != 0.0 && ahead.uniform() < a.xi;
             const double u = ahead.uniform();
             const double fu = biased ? -u : u, fthr = E.fillThreshold(p);
-            RayRec* rec = a.rays + fillAt;
-            if (kEnterInEvent<GRID>) {
-                a.fuseU[slot] = fu;
-                a.fuseThr[slot] = fthr;
-            } else {
-                rec->s0 = fthr;
-                rec->ci = __double2loint(fu);
-                rec->cj = __double2hiint(fu);
-            }
+            a.fuseU[slot] = fu;
+            a.fuseThr[slot] = fthr;
         }
     }
     const unsigned long long vals[8] = {E.packets, E.segFill, E.segWalk, E.segPeel, E.detects, 0, 0, 0};
@@ -1976,7 +2046,7 @@ __global__ void __launch_bounds__(kBlock) contKernel(const Args a) {
                     const unsigned level = (unsigned)min(p.nscatt + 1, 255);
                     const unsigned flags = RAY_PEEL | (cat << 2) | ((unsigned)i << 4) | (level << 10) | ((unsigned)p.ell << 18);
                     a.det[dpos] = DetRec{Lp, 0.0, l, flags};
-                    E.emitRay(pos++, q, ins.kobs[0], ins.kobs[1], ins.kobs[2], Lp, (int)dpos, flags, qcell);
+                    E.emitRay(pos++, q, ins.kobs[0], ins.kobs[1], ins.kobs[2], Lp, (int)dpos, flags, qcell, slot);
                     dpos++;
                 }
             }
@@ -2089,6 +2159,7 @@ struct SkirtMcrt {
     std::vector<hipEvent_t> pollEv;      // kPollRing events behind the counter copies
     // slot pool
     int nslots = 0, rayCap = 0;
+    bool poolRefs = false;  // the pool's ray queue holds RayRef records (16 bytes), not RayRec (80)
     bool poolPath = false;  // the pool holds the continuous-scattering path records
     bool poolDetPair = false;  // the pool holds two detection-record regions (one per iteration parity)
     bool poolPol = false;      // the pool holds the Stokes arrays of a polarised simulation
@@ -2234,11 +2305,12 @@ const void* traceKernelOf(int kind, bool one, bool continuous, bool global, bool
 // bytes they take; with a null base it only counts them (ensurePool). The records of 16-byte alignment come
 // first, from the allocation's start, each a whole number of 16-byte chunks; then the arrays of doubles, then
 // the 4-byte ones. The path records are aligned again: that padding comes out of the kPoolSpare bytes.
-static_assert(sizeof(RayRec) % 16 == 0 && alignof(RayRec) == 16 && sizeof(DetRec) % 16 == 0 && alignof(DetRec) == 16 &&
-                  alignof(PathRec) <= 16,
+// The ray queue holds rayCap records of the phase's format: references (refs, kRayRefs) or whole records.
+static_assert(sizeof(RayRec) % 16 == 0 && alignof(RayRec) == 16 && sizeof(RayRef) % 16 == 0 && alignof(RayRef) == 16 &&
+                  sizeof(DetRec) % 16 == 0 && alignof(DetRec) == 16 && alignof(PathRec) <= 16,
               "pool order: ray records, detection records, 8-byte arrays, 4-byte arrays, aligned path records");
 constexpr size_t kPoolSpare = 4096;
-size_t poolLayout(char* base, size_t nslots, size_t rayCap, bool detPair, bool path, bool pol, Args& a) {
+size_t poolLayout(char* base, size_t nslots, size_t rayCap, bool refs, bool detPair, bool path, bool pol, Args& a) {
     char* p = base;
     size_t bytes = 0;
     auto take = [&](auto*& d, size_t count) {
@@ -2247,7 +2319,13 @@ size_t poolLayout(char* base, size_t nslots, size_t rayCap, bool detPair, bool p
         if (base) p += count * sizeof(T);
         bytes += count * sizeof(T);
     };
-    take(a.rays, rayCap);
+    if (refs) {
+        RayRef* queue = nullptr;
+        take(queue, rayCap);
+        a.rays = reinterpret_cast<RayRec*>(queue);
+    } else {
+        take(a.rays, rayCap);
+    }
     // at most one peel-off per instrument and slot per iteration, in one region or one per iteration parity
     take(a.det, (detPair ? 2 : 1) * (rayCap - nslots));
     for (double** d : {&a.srx, &a.sry, &a.srz, &a.skx, &a.sky, &a.skz, &a.sL, &a.sLth, &a.resA, &a.resB, &a.resS, &a.fuseU,
@@ -2283,11 +2361,14 @@ int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair, bool pol
     if (rays >= (size_t)INT32_MAX) return fail(c, SKIRT_ERR_UNSUPPORTED, "ray queue too large");
     const int rayCap = (int)rays;
     const bool path = continuous && nslots > 0;
-    if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolPath == path && c->poolDetPair == detPair &&
-        c->poolPol == pol)
+    // the queue's format, as the kernels choose it (kRayRefs)
+    const bool refs = !continuous && c->gridKind != SKIRT_GRID_VORONOI;
+    if (c->dPool && c->nslots == nslots && c->rayCap == rayCap && c->poolRefs == refs && c->poolPath == path &&
+        c->poolDetPair == detPair && c->poolPol == pol)
         return SKIRT_OK;
     Args counted{};
-    const size_t bytes = poolLayout(nullptr, (size_t)nslots, (size_t)rayCap, detPair, path, pol, counted) + kPoolSpare;
+    const size_t bytes = poolLayout(nullptr, (size_t)nslots, (size_t)rayCap, refs, detPair, path, pol, counted) + kPoolSpare;
+    c->poolRefs = refs;
     c->poolPath = path;
     c->poolPol = pol;
     c->poolDetPair = detPair;
@@ -2300,7 +2381,8 @@ int ensurePool(SkirtMcrt* c, int nslots, bool continuous, bool detPair, bool pol
 }
 
 void carvePool(SkirtMcrt* c, Args& a) {
-    poolLayout(static_cast<char*>(c->dPool), (size_t)c->nslots, (size_t)c->rayCap, c->poolDetPair, c->poolPath, c->poolPol, a);
+    poolLayout(static_cast<char*>(c->dPool), (size_t)c->nslots, (size_t)c->rayCap, c->poolRefs, c->poolDetPair, c->poolPath,
+               c->poolPol, a);
     a.nslots = c->nslots;
     a.rayCap = c->rayCap;
     a.ctr = c->dCtr;
