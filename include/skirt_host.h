@@ -135,6 +135,13 @@ int skirt_sim_scatterings(SkirtSim* sim, int instrument, int device, size_t n, c
  * host's position templates on the same per-packet streams. pos is n x 3, draws n (or NULL). */
 int skirt_sim_sample_positions(SkirtSim* sim, int comp, int device, uint64_t seed, uint64_t first, size_t n,
                                double* pos, int32_t* draws);
+/* Launches of stellar component `comp` and its probabilityForDirection (skirt_mcrt_sample_launches, which documents
+ * the arguments): on the attached engine of HIP device `device`, or with device < 0 on the host, through the host's
+ * compilation of the same routines (device/aniso_emission.hpp; the host's position templates and Random::direction
+ * for the isotropic kinds) on the same per-packet streams. */
+int skirt_sim_sample_launches(SkirtSim* sim, int comp, int device, uint64_t seed, uint64_t first, size_t n, double* pos,
+                              double* dir, int32_t* draws, size_t nprob, const double* prob_pos, const double* prob_dir,
+                              double* prob);
 
 /* The cross-GPU sums in C++: RCCL (NCCL API) all-reduces over xGMI, the MI355X counterpart of the
  * reference's MPI_Allreduce of the absorption tables and instrument arrays (PanDustSystem.cpp:394-404,

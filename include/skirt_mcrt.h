@@ -55,7 +55,11 @@ enum { SKIRT_GRID_CARTESIAN = 0, SKIRT_GRID_OCTREE = 1, SKIRT_GRID_VORONOI = 2, 
 enum { SKIRT_TREE_TOPDOWN = 0, SKIRT_TREE_NEIGHBOR = 1, SKIRT_TREE_BOOKKEEPING = 2 /* octrees only */ };
 enum { SKIRT_GEOM_PLUMMER = 0, SKIRT_GEOM_EXPDISK = 1, SKIRT_GEOM_SERSIC = 2, SKIRT_GEOM_POINT = 3,
        SKIRT_GEOM_SHELL = 4, SKIRT_GEOM_GAMMA = 5, SKIRT_GEOM_GAUSSIAN = 6, SKIRT_GEOM_TTAURIDISK = 7,
-       SKIRT_GEOM_TORUS = 8, SKIRT_GEOM_CONICALSHELL = 9 };
+       SKIRT_GEOM_TORUS = 8, SKIRT_GEOM_CONICALSHELL = 9,
+       /* sources only, emitting anisotropically (AngularDistribution): NetzerAccretionDiskGeometry,
+          StellarSurfaceGeometry, SpheBackgroundGeometry, CubBackgroundGeometry, SolarPatchGeometry, LaserGeometry */
+       SKIRT_GEOM_NETZER = 10, SKIRT_GEOM_STELLARSURFACE = 11, SKIRT_GEOM_SPHEBACKGROUND = 12,
+       SKIRT_GEOM_CUBBACKGROUND = 13, SKIRT_GEOM_SOLARPATCH = 14, SKIRT_GEOM_LASER = 15 };
 enum { SKIRT_INSTR_FULL = 0, SKIRT_INSTR_SIMPLE = 1, SKIRT_INSTR_SED = 2, SKIRT_INSTR_FRAME = 3 };
 enum { SKIRT_PHASE_STELLAR = 0, SKIRT_PHASE_DUST_EMISSION = 1, SKIRT_PHASE_DUST_SELFABS = 2 };
 
@@ -131,7 +135,14 @@ typedef struct {
                                    GaussianGeometry {sigma, q, rho0, 0...};
                                    TTauriDiskGeometry {Rinn, Rout, Rd, zd, rho0, 0, 0, 0};
                                    TorusGeometry and ConicalShellGeometry {p, q, rmin, rmax, rani (0 or 1),
-                                   rcut, A, 0} (the rest in geom_table). The eighth word is the engine's. */
+                                   rcut, A, 0} (the rest in geom_table);
+                                   StellarSurfaceGeometry, SpheBackgroundGeometry and SolarPatchGeometry {radius, 0...};
+                                   CubBackgroundGeometry {extent, 0...}; NetzerAccretionDiskGeometry and
+                                   LaserGeometry {0...}. A component of one of these six kinds launches its packets
+                                   in the direction of its generateDirection, and its emission peel-offs carry its
+                                   probabilityForDirection towards the instrument (GeometricStellarComp::launch,
+                                   PhotonPackage::launchEmissionPeelOff); a stellar phase with such a component on a
+                                   Voronoi grid is refused (SKIRT_ERR_UNSUPPORTED). The eighth word is the engine's. */
     const double* lum;          /* ncomp x nlambda, W */
     const double* lumtot;       /* nlambda, sum over components */
     const double* cdf;          /* nlambda x (ncomp+1) normalized cumulative luminosity */
@@ -331,6 +342,21 @@ int skirt_mcrt_sample_density(int device, const SkirtDensityDesc* dens, const do
 #define SKIRT_POSITIONS_TAG 0x504f5331u
 int skirt_mcrt_sample_positions(SkirtMcrt* ctx, int comp, uint64_t seed, uint64_t first, size_t n, double* pos,
                                 int32_t* draws);
+
+/* GeometricStellarComp::launch of source component `comp`, as the event kernel of a phase with an anisotropic
+ * component runs it: packet first + i draws from a fresh stream PacketRng::start(seed, SKIRT_LAUNCHES_TAG, first + i);
+ * pos[3 i ..] receives its position (Geometry::generatePosition), dir[3 i ..] its direction (generateDirection of
+ * the six anisotropic kinds at that position, Random::direction() of the others) and draws[i] (if not NULL) the
+ * number of uniform deviates consumed. Then, by the emission peel-off's routine, prob[j] = probabilityForDirection
+ * of direction prob_dir[3 j ..] at position prob_pos[3 j ..] for j < nprob (1 for an isotropic kind); prob_pos NULL
+ * takes the positions just launched (nprob <= n). A prob_pos entry where the reference's function throws (off the
+ * sphere by more than 1e-8 of its radius, off the cube, off the origin for the disk and the laser) fails the call
+ * with SKIRT_ERR_ARG and the reference's message before anything runs. n or nprob may be 0. Synchronous.
+ * skirt_mcrt_sample_positions refuses a component of an anisotropic kind (SKIRT_ERR_UNSUPPORTED). */
+#define SKIRT_LAUNCHES_TAG 0x4c4e4331u
+int skirt_mcrt_sample_launches(SkirtMcrt* ctx, int comp, uint64_t seed, uint64_t first, size_t n, double* pos,
+                               double* dir, int32_t* draws, size_t nprob, const double* prob_pos,
+                               const double* prob_dir, double* prob);
 
 /* Polarised scattering (StokesVector.cpp; DustMix.cpp:96-140, 541-670, 716-731; MonteCarloSimulation.cpp:347-360;
  * FullInstrument.cpp:79-87, 136-141): per dust component its Mueller matrix elements at ntheta scattering angles

@@ -13,6 +13,7 @@
 #include "DistantInstrument.hpp"
 #include "DustMix.hpp"
 #include "ConicalShellGeometry.hpp"
+#include "CubBackgroundGeometry.hpp"
 #include "DustSystem.hpp"
 #include "ExpDiskGeometry.hpp"
 #include "FatalError.hpp"
@@ -22,11 +23,16 @@
 #include "GaussianGeometry.hpp"
 #include "GeometricStellarComp.hpp"
 #include "InstrumentSystem.hpp"
+#include "LaserGeometry.hpp"
 #include "MoveableMesh.hpp"
 #include "NR.hpp"
+#include "NetzerAccretionDiskGeometry.hpp"
 #include "PanDustSystem.hpp"
 #include "PlummerGeometry.hpp"
 #include "PointGeometry.hpp"
+#include "SolarPatchGeometry.hpp"
+#include "SpheBackgroundGeometry.hpp"
+#include "StellarSurfaceGeometry.hpp"
 #include "SEDInstrument.hpp"
 #include "SersicFunction.hpp"
 #include "SersicGeometry.hpp"
@@ -513,6 +519,35 @@ void GpuPhotonEngine::describeSources()
             t[1] = cg->_sinDeltaIn;
             t[2] = cg->_smin;
             t[3] = cg->_sdiff;
+        }
+        // the sources that emit anisotropically (AngularDistribution): the one parameter in the row's first word
+        else if (dynamic_cast<NetzerAccretionDiskGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_NETZER;
+        }
+        else if (StellarSurfaceGeometry* ssg = dynamic_cast<StellarSurfaceGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_STELLARSURFACE;
+            p[0] = ssg->radius();
+        }
+        else if (SpheBackgroundGeometry* sbg = dynamic_cast<SpheBackgroundGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_SPHEBACKGROUND;
+            p[0] = sbg->radius();
+        }
+        else if (CubBackgroundGeometry* cbg = dynamic_cast<CubBackgroundGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_CUBBACKGROUND;
+            p[0] = cbg->extent();
+        }
+        else if (SolarPatchGeometry* spg = dynamic_cast<SolarPatchGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_SOLARPATCH;
+            p[0] = spg->radius();
+        }
+        else if (dynamic_cast<LaserGeometry*>(geo))
+        {
+            kind[h] = SKIRT_GEOM_LASER;
         }
         else
         {

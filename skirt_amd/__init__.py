@@ -28,6 +28,9 @@ GRID_CARTESIAN, GRID_OCTREE, GRID_VORONOI, GRID_CYLINDER2D, GRID_SPHERE1D, GRID_
 # SKIRT_GEOM_*: the geometry kinds of stellar and dust components
 (GEOM_PLUMMER, GEOM_EXPDISK, GEOM_SERSIC, GEOM_POINT, GEOM_SHELL, GEOM_GAMMA, GEOM_GAUSSIAN, GEOM_TTAURIDISK,
  GEOM_TORUS, GEOM_CONICALSHELL) = range(10)
+# sources only, emitting anisotropically (AngularDistribution)
+(GEOM_NETZER, GEOM_STELLARSURFACE, GEOM_SPHEBACKGROUND, GEOM_CUBBACKGROUND, GEOM_SOLARPATCH,
+ GEOM_LASER) = range(10, 16)
 # SkirtStats.grid_walk: the trace kernel's grid walk in the last run (SKIRT_WALK_*)
 WALK_CARTESIAN, WALK_OCTREE_MAP, WALK_VORONOI, WALK_TREE_NODES, WALK_KDTREE_MAP, WALK_OCTREE_BOOKKEEPING = 0, 1, 2, 3, 4, 5
 
@@ -78,6 +81,7 @@ ABI_SYMBOLS = [
     "skirt_mcrt_sample_positions", "skirt_sim_sample_positions",
     "skirt_mcrt_set_mueller", "skirt_mcrt_scatterings", "skirt_sim_polarization", "skirt_sim_scatterings",
     "skirt_host_write_mueller",
+    "skirt_mcrt_sample_launches", "skirt_sim_sample_launches",
 ]
 
 _lib = None
@@ -138,6 +142,12 @@ def lib():
                                                      ctypes.POINTER(c_dbl), ctypes.POINTER(ctypes.c_int32)]
             L.skirt_mcrt_sample_positions.argtypes = [vp, c_int, c_u64, c_u64, ctypes.c_size_t, ctypes.POINTER(c_dbl),
                                                       ctypes.POINTER(ctypes.c_int32)]
+        if hasattr(L, "skirt_sim_sample_launches"):  # (likewise)
+            dp, sz = ctypes.POINTER(c_dbl), ctypes.c_size_t
+            L.skirt_sim_sample_launches.argtypes = [vp, c_int, c_int, c_u64, c_u64, sz, dp, dp,
+                                                    ctypes.POINTER(ctypes.c_int32), sz, dp, dp, dp]
+            L.skirt_mcrt_sample_launches.argtypes = [vp, c_int, c_u64, c_u64, sz, dp, dp, ctypes.POINTER(ctypes.c_int32),
+                                                     sz, dp, dp, dp]
         if hasattr(L, "skirt_sim_scatterings"):  # (likewise)
             L.skirt_sim_polarization.argtypes = [vp]
             L.skirt_sim_scatterings.argtypes = [vp, c_int, c_int, ctypes.c_size_t] + [ctypes.POINTER(c_dbl)] * 3
@@ -335,6 +345,40 @@ class Simulation:
             self._h, int(comp), -1 if device is None else int(device), int(seed), int(first), n,
             pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), draws.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return pos, draws
+
+    def launches(self, comp, n, seed=1, first=0, device=None):
+        """n launches of stellar component `comp` (GeometricStellarComp::launch) on the per-packet streams
+        first .. first + n - 1 of `seed`: (pos [n, 3], dir [n, 3], draws [n]) -- Geometry::generatePosition, then the
+        direction (generateDirection at that position for the six anisotropic kinds, Random::direction() for the
+        others) and the uniform deviates both consumed. device=None runs the host's routines; a device runs the
+        engine's launch routine there (attaching to it when no engine is attached yet)."""
+        n = int(n)
+        pos, dirs = np.zeros((n, 3)), np.zeros((n, 3))
+        draws = np.zeros(n, dtype=np.int32)
+        if device is not None and not self.attached:
+            self.attach(int(device))
+        dp = ctypes.POINTER(ctypes.c_double)
+        self._check(lib().skirt_sim_sample_launches(
+            self._h, int(comp), -1 if device is None else int(device), int(seed), int(first), n, pos.ctypes.data_as(dp),
+            dirs.ctypes.data_as(dp), draws.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), 0, None, None, None))
+        return pos, dirs, draws
+
+    def emission_probability(self, comp, pos, dirs, device=None):
+        """probabilityForDirection of stellar component `comp` for directions dirs [n, 3] at positions pos [n, 3] (or
+        one position [3] for all): the factor an emission peel-off towards that direction carries, 1 for an isotropic
+        kind. A position where the reference's function throws (off the sphere by more than 1e-8 of its radius, off
+        the cube, off the origin for the disk and the laser) raises SkirtError with the reference's message before
+        anything runs. device as in launches()."""
+        k = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(pos, dtype=np.float64).reshape(-1, 3), k.shape))
+        out = np.zeros(len(k))
+        if device is not None and not self.attached:
+            self.attach(int(device))
+        dp = ctypes.POINTER(ctypes.c_double)
+        self._check(lib().skirt_sim_sample_launches(
+            self._h, int(comp), -1 if device is None else int(device), 0, 0, 0, None, None, None, len(k),
+            r.ctypes.data_as(dp), k.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+        return out
 
     @property
     def polarization(self):

@@ -1,6 +1,6 @@
-// The setup's sampling kernels: DensArgs, geomDensity, samplePositionsKernel and densitySampleKernel.
-// Compiles only where engine.hip includes it, inside its anonymous namespace, after Events
-// (Events::launchPosition).
+// The setup's sampling kernels: DensArgs, geomDensity, samplePositionsKernel, sampleLaunchesKernel and
+// densitySampleKernel. Compiles only where engine.hip includes it, inside its anonymous namespace, after Events
+// (Events::launchPosition, launchDirection, emissionProbability).
 #ifndef SKIRT_AMD_DEVICE_DENSITY_SAMPLE_HPP
 #define SKIRT_AMD_DEVICE_DENSITY_SAMPLE_HPP
 
@@ -83,6 +83,34 @@ __global__ void __launch_bounds__(kBlock)
         atomicOr(error, ERR_GEOM);
     pos[3 * i] = x; pos[3 * i + 1] = y; pos[3 * i + 2] = z;
     draws[i] = (int)(2u * rng.block - (rng.have ? 1u : 0u));
+}
+
+// GeometricStellarComp::launch of one source component on fresh per-packet streams (skirt_mcrt_sample_launches): the
+// position and the direction by the routines Events::launchStellar runs in a phase with an anisotropic component,
+// one packet per thread; then probabilityForDirection, by the emission peel-off's routine, of nprob given
+// directions at given positions (ppos) or at the positions just launched (ppos null, nprob <= n)
+__global__ void __launch_bounds__(kBlock)
+    sampleLaunchesKernel(const double* geomParam, const double* geomTable, int nstar, int h, unsigned long long seed,
+                         unsigned long long first, size_t n, double* pos, double* dir, int* draws, size_t nprob,
+                         const double* ppos, const double* pdir, double* prob, unsigned* error) {
+    using E = Events<SKIRT_GRID_CARTESIAN, true, false, true>;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const double* gp = geomParam + 8 * h;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (i < n) {
+        PacketRng rng;
+        rng.start(seed, SKIRT_LAUNCHES_TAG, first + i);
+        double kx = 0.0, ky = 0.0, kz = 1.0;
+        if (!E::launchPosition(gp, geomTable, h, rng, x, y, z)) atomicOr(error, ERR_GEOM);
+        else E::launchDirection(gp, geomParam + 8 * nstar, rng, x, y, z, kx, ky, kz);
+        pos[3 * i] = x; pos[3 * i + 1] = y; pos[3 * i + 2] = z;
+        dir[3 * i] = kx; dir[3 * i + 1] = ky; dir[3 * i + 2] = kz;
+        draws[i] = (int)(2u * rng.block - (rng.have ? 1u : 0u));
+    }
+    if (i < nprob) {
+        if (ppos) { x = ppos[3 * i]; y = ppos[3 * i + 1]; z = ppos[3 * i + 2]; }
+        prob[i] = E::emissionProbability(gp, x, y, z, pdir[3 * i], pdir[3 * i + 1], pdir[3 * i + 2]);
+    }
 }
 
 __global__ void __launch_bounds__(kBlock) densitySampleKernel(const DensArgs d) {

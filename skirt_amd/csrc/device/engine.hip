@@ -37,6 +37,7 @@
 #include "cyl2d_walk.hpp"
 #include "sph_walk.hpp"
 #include "geom_sample.hpp"
+#include "aniso_emission.hpp"
 #include "polarization.hpp"
 #include "../../../include/skirt_mcrt.h"
 #include "philox.hpp"
@@ -98,8 +99,15 @@ constexpr int kPollRing = 3;       // copies in flight (the host reads each kPol
 #endif
 // One instantiation runs at 1: polarised with several components on a Voronoi grid. It needs 278 registers (256
 // VGPRs + 22 AGPRs); held to 2 waves it keeps 96 bytes of scratch per lane ("Registers")
-#define SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, POL) \
-    __attribute__((amdgpu_waves_per_eu(((POL) && !(ONECOMP) && (GRID) == SKIRT_GRID_VORONOI) ? 1 : SKIRT_EVENT_WAVES)))
+// So do the polarised kernels of an anisotropic source (ANISO) with several components: at 2 waves five of the
+// eight keep 12-24 bytes of scratch per lane (profiles/aniso_first.txt)
+#define SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, POL, ANISO) \
+    __attribute__((amdgpu_waves_per_eu(                  \
+        ((POL) && !(ONECOMP) && ((ANISO) || (GRID) == SKIRT_GRID_VORONOI)) ? 1 : SKIRT_EVENT_WAVES)))
+// Whether the anisotropic event kernels (ANISO) exist for a grid: not for Voronoi grids, whose event kernel enters
+// the grid itself and has no registers left (above); such a phase is refused (runPhase)
+template <int GRID>
+constexpr bool kAnisoGrid = GRID != SKIRT_GRID_VORONOI;
 
 // ------------------------------------------------------------------ descriptors
 struct DevInstr {
@@ -169,6 +177,10 @@ static_assert(GEOMS_SHELL == SKIRT_GEOM_SHELL && GEOMS_GAMMA == SKIRT_GEOM_GAMMA
                   GEOMS_TTAURIDISK == SKIRT_GEOM_TTAURIDISK && GEOMS_TORUS == SKIRT_GEOM_TORUS &&
                   GEOMS_CONICALSHELL == SKIRT_GEOM_CONICALSHELL,
               "geom_sample.hpp follows the kinds of skirt_mcrt.h");
+static_assert(ANISO_NETZER == SKIRT_GEOM_NETZER && ANISO_STELLARSURFACE == SKIRT_GEOM_STELLARSURFACE &&
+                  ANISO_SPHEBACKGROUND == SKIRT_GEOM_SPHEBACKGROUND && ANISO_CUBBACKGROUND == SKIRT_GEOM_CUBBACKGROUND &&
+                  ANISO_SOLARPATCH == SKIRT_GEOM_SOLARPATCH && ANISO_LASER == SKIRT_GEOM_LASER,
+              "aniso_emission.hpp follows the kinds of skirt_mcrt.h");
 template <int GRID>
 constexpr bool kEnterInEvent = GRID == SKIRT_GRID_VORONOI;
 // the queue's format (RayRef or RayRec): CONT is the trace kernels' template argument; in the event kernel,
@@ -1116,7 +1128,10 @@ struct PolDrawsStream {
 
 // POL: a simulation whose dust mixes polarise (Args::pol): the packet carries a Stokes vector, scatters by the
 // Mueller tables and its peel-offs carry Q, U, V. POL = false is the code as it was.
-template <int GRID, bool ONECOMP, bool POL = false>
+// ANISO: a stellar phase one of whose components emits anisotropically (aniso_emission.hpp): the launch takes the
+// direction from the component's kind and an emission peel-off carries its probabilityForDirection. ANISO = false
+// is the code as it was: those kinds are then neither launched nor weighted (upload_sources and runPhase see to it).
+template <int GRID, bool ONECOMP, bool POL = false, bool ANISO = false>
 struct Events {
     const Args& a;
     const Shared& sh;
@@ -1548,6 +1563,12 @@ struct Events {
         // the six closed-form kinds (geom_sample.hpp), the torus and the cone (the rest of whose constants start
         // their geom_table row) apart from the other four: dispatched this way every event kernel keeps its three
         // waves per SIMD (profiles/geom_first.txt). False when a rejection loop reached its cap.
+        if constexpr (ANISO) {
+            if ((int)gp[7] >= SKIRT_GEOM_NETZER) {
+                anisoPositionOf((int)gp[7], gp[0], rng, x, y, z);
+                return true;
+            }
+        }
         if ((int)gp[7] >= SKIRT_GEOM_TORUS) {
             return geomConePosition(gp, geomTable + (size_t)kSersicTable * h, rng, x, y, z);
         } else if ((int)gp[7] >= SKIRT_GEOM_SHELL) {
@@ -1587,6 +1608,39 @@ struct Events {
         return true;
     }
 
+    // GeometricStellarComp::launch's direction for a packet leaving (x, y, z) of the component of row gp:
+    // _geom->generateDirection for the anisotropic kinds (netzer: the table behind the rows, upload_sources),
+    // Random::direction() for the others; shared by launchStellar and skirt_mcrt_sample_launches
+    __device__ __forceinline__ static void launchDirection(const double* gp, const double* netzer, PacketRng& rng,
+                                                           double x, double y, double z, double& kx, double& ky,
+                                                           double& kz) {
+        if constexpr (ANISO) {
+            if ((int)gp[7] >= SKIRT_GEOM_NETZER) {
+                anisoDirectionOf((int)gp[7], gp[0], netzer, rng, x, y, z, kx, ky, kz);
+                return;
+            }
+        }
+        isotropic(rng, kx, ky, kz);
+    }
+    // PhotonPackage::launchEmissionPeelOff's factor for a stellar packet: the component's probabilityForDirection
+    // towards the instrument (1 for an isotropic kind)
+    __device__ __forceinline__ double emissionWeight(const Packet& p, const DevInstr& ins) const {
+        if constexpr (ANISO) {
+            if (p.stellar >= 0)
+                return emissionProbability(a.geomParam + 8 * p.stellar, p.rx, p.ry, p.rz, ins.kobs[0], ins.kobs[1],
+                                           ins.kobs[2]);
+        }
+        return 1.0;
+    }
+    // the same for the component of row gp, a position and a direction; shared with skirt_mcrt_sample_launches
+    __device__ __forceinline__ static double emissionProbability(const double* gp, double x, double y, double z,
+                                                                 double kx, double ky, double kz) {
+        if constexpr (ANISO) {
+            if ((int)gp[7] >= SKIRT_GEOM_NETZER) return anisoProbabilityOf((int)gp[7], gp[0], x, y, z, kx, ky, kz);
+        }
+        return 1.0;
+    }
+
     // StellarSystem::launch + GeometricStellarComp::launch + PlummerGeometry sampling (see below)
     __device__ __forceinline__ bool launchStellar(Packet& p, unsigned long long idx) {
         const int ell = (int)(idx / a.npp);
@@ -1621,8 +1675,8 @@ struct Events {
             atomicOr(a.error, ERR_GEOM);  // a torus or cone whose rejection loop reached its cap: SKIRT_ERR_NUMERIC
             return false;
         }
-        // the emission direction Random::direction()
-        isotropic(p.rng, p.kx, p.ky, p.kz);
+        // the emission direction: Random::direction(), or the component's generateDirection (ANISO)
+        launchDirection(a.geomParam + 8 * h, a.geomParam + 8 * a.nstar, p.rng, p.rx, p.ry, p.rz, p.kx, p.ky, p.kz);
         p.L = L;
         p.nscatt = 0;
         p.stellar = h;
@@ -1703,14 +1757,14 @@ __device__ __forceinline__ unsigned long long globalPacket(const Args& a, unsign
     return ell * a.npp + a.sliceLo + (j - ell * a.sliceCnt);
 }
 
-template <int GRID, bool ONECOMP, bool POL = false>
-__global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, POL) eventKernel(const Args a) {
+template <int GRID, bool ONECOMP, bool POL = false, bool ANISO = false>
+__global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, POL, ANISO) eventKernel(const Args a) {
     __shared__ unsigned long long resv[4 * (kBlock / 64) + 4];
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (blockIdx.x == 0 && threadIdx.x == 0) CTR(a.ctr, CTR_PULL) = 0;
     if (!a.init && CTR(a.ctr, CTR_ACTIVE + a.parity) == 0) return;  // an iteration after the end of the phase
     Shared sh = stageTables(a, lds, gridParts<GRID>() | STAGE_OPTICS | STAGE_INSTR);
-    Events<GRID, ONECOMP, POL> E{a, sh};
+    Events<GRID, ONECOMP, POL, ANISO> E{a, sh};
     const int lane = threadIdx.x & 63;
     const unsigned long long total = a.end - a.first;
     const unsigned int nwork = a.init ? (unsigned)a.nslots : CTR(a.ctr, CTR_ACTIVE + a.parity);
@@ -1837,7 +1891,8 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, PO
                             const DevInstr& ins = sh.instr[i];
                             const int l = ins.kind == SKIRT_INSTR_SED ? -1 : E.pixel(ins, p);
                             if (ins.kind == SKIRT_INSTR_FRAME && l < 0) continue;
-                            E.detectNow(ins, p, p.L, l);
+                            if constexpr (ANISO) E.detectNow(ins, p, p.L * E.emissionWeight(p, ins), l);
+                            else E.detectNow(ins, p, p.L, l);
                         }
                     }
                 }
@@ -1897,6 +1952,7 @@ __global__ void __launch_bounds__(kBlock) SKIRT_EVENT_ATTR_FOR(GRID, ONECOMP, PO
                 unsigned cat, level = 0;
                 DetPol dq{0.0, 0.0, 0.0};  // (an emission peel-off is unpolarized)
                 if (peel == PEEL_EMISSION) {
+                    if constexpr (ANISO) Lp = p.L * E.emissionWeight(p, ins);  // PhotonPackage::launchEmissionPeelOff
                     cat = p.stellar >= 0 ? CAT_STAR_DIRECT : CAT_DUST_DIRECT;
                 } else {
                     double I = 0;
@@ -2119,6 +2175,10 @@ struct SkirtMcrt {
     // keyed by its own index, so skipping them changes no other packet)
     int lumLo = 0, lumHi = -1;
     double* dGeomTable = nullptr;  // SersicGeometry tables, kSersicTable per component
+    // a component of an anisotropic kind (aniso_emission.hpp): the stellar phase runs the ANISO event kernels, and
+    // dGeomParam holds the Netzer table (anisoNetzerWords) behind the components' rows
+    bool anyAniso = false;
+    std::vector<double> geomParamHost;  // the rows of dGeomParam (the launch probe's checks)
     double emissionBias = 0.5;
     // dust-phase cell sources and the dust Labs tally
     double *dCellLv = nullptr, *dCellCdf = nullptr, *dCellLtot = nullptr;
@@ -2964,10 +3024,16 @@ int skirt_mcrt_upload_sources(SkirtMcrt* c, const SkirtSourceDesc* s) {
     if (s->ncomp < 1 || s->nlambda < 1) return fail(c, SKIRT_ERR_ARG, "bad source sizes");
     // device geometry table: the 8 parameters of each component with its kind in the last word
     std::vector<double> gp(8 * (size_t)s->ncomp);
-    bool tables = false;
+    bool tables = false, aniso = false;
     for (int h = 0; h < s->ncomp; h++) {
-        if (s->geom_kind[h] < SKIRT_GEOM_PLUMMER || s->geom_kind[h] > SKIRT_GEOM_CONICALSHELL)
+        if (s->geom_kind[h] < SKIRT_GEOM_PLUMMER || s->geom_kind[h] > SKIRT_GEOM_LASER)
             return fail(c, SKIRT_ERR_UNSUPPORTED, "unsupported source geometry");
+        if (anisoIsKind(s->geom_kind[h])) {
+            aniso = true;
+            const bool sized = s->geom_kind[h] != SKIRT_GEOM_NETZER && s->geom_kind[h] != SKIRT_GEOM_LASER;
+            if (sized && !(s->geom_param[8 * h] > 0))
+                return fail(c, SKIRT_ERR_ARG, "an anisotropic source's radius or extent should be positive");
+        }
         if (s->geom_kind[h] == SKIRT_GEOM_SERSIC) {
             if (!s->geom_table) return fail(c, SKIRT_ERR_ARG, "SersicGeometry without its tables");
             tables = true;
@@ -2979,6 +3045,12 @@ int skirt_mcrt_upload_sources(SkirtMcrt* c, const SkirtSourceDesc* s) {
         for (int q = 0; q < 7; q++) gp[8 * h + q] = s->geom_param[8 * h + q];
         gp[8 * h + 7] = (double)s->geom_kind[h];
     }
+    c->geomParamHost = gp;
+    if (aniso) {  // the Netzer disk's table behind the rows (one copy for every component, 6.4 KB)
+        gp.resize(8 * (size_t)s->ncomp + anisoNetzerWords);
+        anisoNetzerTable(gp.data() + 8 * (size_t)s->ncomp);
+    }
+    c->anyAniso = aniso;
     HIPCHECK(c, hipSetDevice(c->device));
     if (c->nlambda && c->nlambda != s->nlambda) return fail(c, SKIRT_ERR_ARG, "sources and media disagree on nlambda");
     if (s->nlambda >= (1 << 14)) return fail(c, SKIRT_ERR_ARG, "at most 16383 wavelengths");
@@ -3366,6 +3438,7 @@ struct PhasePlan {
     Args a{};  // the kernel arguments, but for the pool (carvePool) and the per-iteration parity, init and det
     int kind = kOctreeNodes;  // the grid walk (kWalks)
     bool continuous = false, noStore = false, detAside = false;
+    bool aniso = false;  // a stellar phase with an anisotropic component: the ANISO event kernels
     size_t ldsTrace = 0, ldsEvent = 0, ldsDetect = 0;  // dynamic LDS of the trace, event / continuous and detect kernels
     const void* traceFn = nullptr;
     int tgrid = 0, egrid = 0, dgrid = 0;  // workgroups of the trace, event / continuous and detect launches
@@ -3525,6 +3598,7 @@ static int planPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint
         a.mapX0 = c->mapOrigin[0]; a.mapY0 = c->mapOrigin[1]; a.mapZ0 = c->mapOrigin[2];
     }
     a.optics = c->dOptics;
+    pl.aniso = c->anyAniso && phase == SKIRT_PHASE_STELLAR;
     a.pol = pol ? 1 : 0;
     a.polTab = pol ? c->dPolTab : nullptr;
     a.polNtheta = c->polNtheta;
@@ -3593,6 +3667,18 @@ static int runIterations(SkirtMcrt* c, const PhasePlan& pl) {
     auto launchEvent = [&](const Args& aa, hipStream_t st) {
         withWalk(kind, [&](auto g) {
             withBool(one, [&](auto o) {
+                constexpr int G = decltype(g)::value;
+                if constexpr (kAnisoGrid<G>) {
+                    if (pl.aniso) {  // (runPhase has refused the grids without these kernels)
+                        if (aa.pol)
+                            hipLaunchKernelGGL((eventKernel<G, decltype(o)::value, true, true>), dim3(pl.egrid), dim3(kBlock),
+                                               pl.ldsEvent, st, aa);
+                        else
+                            hipLaunchKernelGGL((eventKernel<G, decltype(o)::value, false, true>), dim3(pl.egrid),
+                                               dim3(kBlock), pl.ldsEvent, st, aa);
+                        return;
+                    }
+                }
                 if (aa.pol)
                     hipLaunchKernelGGL((eventKernel<decltype(g)::value, decltype(o)::value, true>), dim3(pl.egrid),
                                        dim3(kBlock), pl.ldsEvent, st, aa);
@@ -3727,6 +3813,9 @@ static int runPhase(SkirtMcrt* c, int phase, uint32_t cycle, uint64_t npp, uint6
         return fail(c, SKIRT_ERR_UNSUPPORTED, "continuous scattering is not supported with polarised dust mixes");
     if (c->dPolTab && cellPhase)
         return fail(c, SKIRT_ERR_UNSUPPORTED, "dust emission phases are not supported with polarised dust mixes");
+    // anisotropic sources: every grid but the Voronoi grid (kAnisoGrid)
+    if (c->anyAniso && !cellPhase && c->gridKind == SKIRT_GRID_VORONOI)
+        return fail(c, SKIRT_ERR_UNSUPPORTED, "anisotropic sources are not supported on a Voronoi dust grid");
     if (cellPhase && (!c->dCellLtot || !p->has_dust)) return fail(c, SKIRT_ERR_STATE, "a dust phase needs a dust system and uploaded cell sources");
     if (c->gridKind < 0 && p->has_dust) return fail(c, SKIRT_ERR_STATE, "no grid uploaded");
     if (!cellPhase && !c->dLumtot) return fail(c, SKIRT_ERR_STATE, "no sources uploaded");
@@ -3969,6 +4058,8 @@ int skirt_mcrt_sample_positions(SkirtMcrt* c, int comp, uint64_t seed, uint64_t 
     if (!c) return SKIRT_ERR_ARG;
     if (!c->dGeomParam || c->nstar < 1) return fail(c, SKIRT_ERR_STATE, "sample_positions before upload_sources");
     if (comp < 0 || comp >= c->nstar || (n && !pos)) return fail(c, SKIRT_ERR_ARG, "bad component or buffer");
+    if (anisoIsKind((int)c->geomParamHost[8 * (size_t)comp + 7]))  // (its kernel is the isotropic launch's)
+        return fail(c, SKIRT_ERR_UNSUPPORTED, "sample_positions: an anisotropic component's positions come with its launches (sample_launches)");
     if (n == 0) return SKIRT_OK;
     const size_t nblocks = (n + kBlock - 1) / kBlock;
     if (nblocks > 0x7fffffffu) return fail(c, SKIRT_ERR_ARG, "too many positions");
@@ -3997,6 +4088,72 @@ int skirt_mcrt_sample_positions(SkirtMcrt* c, int comp, uint64_t seed, uint64_t 
     if (dPos) (void)hipFree(dPos);
     if (dDraws) (void)hipFree(dDraws);
     if (dErr) (void)hipFree(dErr);
+    return rc;
+}
+
+// the reference's message for a position where a kind's generateDirection / probabilityForDirection throws; null
+// where the position is accepted
+static const char* anisoPositionError(int kind, double r0, const double* p) {
+    if (!anisoIsKind(kind) || anisoPositionValid(kind, r0, p[0], p[1], p[2])) return nullptr;
+    switch (kind) {
+    case SKIRT_GEOM_STELLARSURFACE:
+        return "the directional probability function is not defined for positions not on the stellar surface";
+    case SKIRT_GEOM_SPHEBACKGROUND:
+        return "the directional probability function is not defined for positions not on the background sphere";
+    case SKIRT_GEOM_CUBBACKGROUND:
+        return "the directional probability function is not defined for positions not on the background cube";
+    default: return "the angular probability function is not defined for positions besides the origin";
+    }
+}
+
+int skirt_mcrt_sample_launches(SkirtMcrt* c, int comp, uint64_t seed, uint64_t first, size_t n, double* pos, double* dir,
+                               int32_t* draws, size_t nprob, const double* prob_pos, const double* prob_dir,
+                               double* prob) {
+    if (!c) return SKIRT_ERR_ARG;
+    if (!c->dGeomParam || c->nstar < 1) return fail(c, SKIRT_ERR_STATE, "sample_launches before upload_sources");
+    if (comp < 0 || comp >= c->nstar || (n && (!pos || !dir)) || (nprob && (!prob_dir || !prob)) ||
+        (nprob && !prob_pos && nprob > n))
+        return fail(c, SKIRT_ERR_ARG, "bad component or buffer");
+    const double* gph = c->geomParamHost.data() + 8 * (size_t)comp;
+    if (prob_pos)  // checked on the host, before any launch
+        for (size_t i = 0; i < nprob; i++)
+            if (const char* msg = anisoPositionError((int)gph[7], gph[0], prob_pos + 3 * i)) return fail(c, SKIRT_ERR_ARG, msg);
+    const size_t nthreads = std::max(n, nprob);
+    if (nthreads == 0) return SKIRT_OK;
+    const size_t nblocks = (nthreads + kBlock - 1) / kBlock;
+    if (nblocks > 0x7fffffffu) return fail(c, SKIRT_ERR_ARG, "too many launches");
+    HIPCHECK(c, hipSetDevice(c->device));
+    // one allocation: positions, directions, probabilities' inputs and outputs, then the draws and the error word
+    const size_t offPos = 0, offDir = offPos + 3 * n, offPpos = offDir + 3 * n, offPdir = offPpos + (prob_pos ? 3 * nprob : 0),
+                 offProb = offPdir + 3 * nprob, nd = offProb + nprob;
+    const size_t bytes = nd * sizeof(double) + (n + 1) * sizeof(int);
+    double* buf = nullptr;
+    unsigned err = 0;
+    int rc = SKIRT_OK;
+    if (hipMalloc(&buf, bytes) != hipSuccess) return fail(c, SKIRT_ERR_HIP, "sample_launches: allocation failed");
+    int* dDraws = reinterpret_cast<int*>(buf + nd);
+    unsigned* dErr = reinterpret_cast<unsigned*>(dDraws + n);
+    if (hipMemsetAsync(dErr, 0, sizeof(unsigned), c->stream) != hipSuccess ||
+        (prob_pos && hipMemcpyAsync(buf + offPpos, prob_pos, 3 * nprob * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+        (nprob && hipMemcpyAsync(buf + offPdir, prob_dir, 3 * nprob * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess)) {
+        rc = fail(c, SKIRT_ERR_HIP, "sample_launches: a copy failed");
+    } else {
+        hipLaunchKernelGGL(sampleLaunchesKernel, dim3((unsigned)nblocks), dim3(kBlock), 0, c->stream, c->dGeomParam,
+                           c->dGeomTable, c->nstar, comp, (unsigned long long)seed, (unsigned long long)first, n, buf + offPos,
+                           buf + offDir, dDraws, nprob, prob_pos ? buf + offPpos : nullptr, buf + offPdir, buf + offProb, dErr);
+        if (hipGetLastError() != hipSuccess ||
+            (n && hipMemcpyAsync(pos, buf + offPos, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+            (n && hipMemcpyAsync(dir, buf + offDir, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+            (n && draws && hipMemcpyAsync(draws, dDraws, n * sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+            (nprob && hipMemcpyAsync(prob, buf + offProb, nprob * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+            hipMemcpyAsync(&err, dErr, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess)
+            rc = fail(c, SKIRT_ERR_HIP, "sample_launches: the kernel or a copy failed");
+        else if (err & ERR_GEOM)
+            rc = fail(c, SKIRT_ERR_NUMERIC, kGeomCapMessage);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
     return rc;
 }
 

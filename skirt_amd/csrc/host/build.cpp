@@ -271,6 +271,14 @@ double Geometry::density(double x, double y, double z) const {
         if (kind == GeometryKind::ConicalShell && std::fabs(costheta) <= sinDeltaIn) return 0.0;
         return A * std::pow(r, -p) * std::exp(-q * std::fabs(costheta));
     }
+    case GeometryKind::Netzer:
+    case GeometryKind::StellarSurface:
+    case GeometryKind::SpheBackground:
+    case GeometryKind::CubBackground:
+    case GeometryKind::SolarPatch:
+    case GeometryKind::Laser:
+        // a point, a surface or a patch: infinite there and 0 elsewhere; never asked, these kinds are sources only
+        throw std::runtime_error("an anisotropic source geometry has no density to sample");
     }
     return 0;
 }
@@ -802,6 +810,26 @@ Geometry parseGeometry(const Ctx& c, const XmlElement* g) {
             else geo.A = 0.25 / M_PI / geo.sdiff / geo.sinDelta;
         }
         checkAcceptance(geo, g->name);
+    } else if (g->name == "NetzerAccretionDiskGeometry") {
+        geo.kind = GeometryKind::Netzer;  // (its 401-entry table has no parameters: anisoNetzerTable)
+    } else if (g->name == "LaserGeometry") {
+        geo.kind = GeometryKind::Laser;
+    } else if (g->name == "StellarSurfaceGeometry") {
+        geo.kind = GeometryKind::StellarSurface;
+        geo.r0 = attr(c, g, "radius", "length", 0);
+        if (geo.r0 <= 0) throw std::runtime_error("the stellar radius rstar should be positive");
+    } else if (g->name == "SpheBackgroundGeometry") {
+        geo.kind = GeometryKind::SpheBackground;
+        geo.r0 = attr(c, g, "radius", "length", 0);
+        if (geo.r0 <= 0) throw std::runtime_error("the background sphere radius rbg should be positive");
+    } else if (g->name == "CubBackgroundGeometry") {
+        geo.kind = GeometryKind::CubBackground;
+        geo.r0 = attr(c, g, "extent", "length", 0);
+        if (geo.r0 <= 0) throw std::runtime_error("the background cube extent h should be positive");
+    } else if (g->name == "SolarPatchGeometry") {
+        geo.kind = GeometryKind::SolarPatch;
+        geo.r0 = attr(c, g, "radius", "length", 0);
+        if (geo.r0 <= 0) throw std::runtime_error("the patch radius Rmax should be positive");
     } else {
         throw std::runtime_error("unsupported geometry " + g->name);
     }
@@ -1783,6 +1811,8 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
             comp.geom = parseGeometry(c, need(dc, "geometry"));
             if (comp.geom.kind == GeometryKind::Point)  // a delta density cannot be sampled on a dust grid
                 throw std::runtime_error("PointGeometry is not supported for dust components");
+            if (isAnisotropic(comp.geom.kind))  // (densities 0 or infinite as well)
+                throw std::runtime_error(need(dc, "geometry")->name + " is not supported for dust components");
             comp.mix = parseMix(c, need(dc, "mix"), m.wl);
             const XmlElement* nrm = need(dc, "normalization");
             if (nrm->name == "DustMassDustCompNormalization") {
@@ -1817,6 +1847,21 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
             throw std::runtime_error("dust emission is not supported with polarised dust mixes (ElectronDustMix)");
 
         const XmlElement* ge = need(ds, "dustGrid");
+        // DustGrid::setupSelfBefore (DustGrid.cpp:33-38), before the grid is built, for the anisotropic sources
+        // only (for the other kinds models load as they did): the grid has at least the dimension of the geometry
+        {
+            const int dimGrid = ge->name == "Sphere1DDustGrid" ? 1
+                                : (ge->name == "Sphere2DDustGrid" || ge->name == "Cylinder2DDustGrid") ? 2 : 3;
+            int dimGeometry = 0;
+            for (const Geometry& sg : m.starGeom)
+                if (isAnisotropic(sg.kind)) dimGeometry = std::max(dimGeometry, anisoDimension(sg.kind));
+            if (dimGeometry > dimGrid)
+                throw std::runtime_error("The grid dimension " + std::to_string(dimGrid) +
+                                         " is lower than the geometry dimension " + std::to_string(dimGeometry));
+            // the engine's own limit: the Voronoi grid's event kernel has no anisotropic instantiation
+            if (dimGeometry > 0 && ge->name == "VoronoiDustGrid")
+                throw std::runtime_error("anisotropic sources are not supported on a VoronoiDustGrid");
+        }
         if (ge->name == "CartesianDustGrid") {
             m.grid.kind = GridKind::Cartesian;
             CartesianGrid& g = m.grid.cart;

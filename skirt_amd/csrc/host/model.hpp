@@ -14,6 +14,7 @@
 #include "mt_random.hpp"
 #include "units.hpp"
 #include "voronoi.hpp"
+#include "../device/aniso_emission.hpp"
 
 namespace skirt {
 
@@ -31,10 +32,21 @@ namespace skirt {
 // (SepAxGeometry: R, phi, z), TTauriDiskGeometry.cpp and TorusGeometry.cpp, ConicalShellGeometry.cpp (AxGeometry with
 // a generatePosition of their own; the last two reject positions by their density), with SpecialFunctions::gln /
 // gln2 / gexp and Random::gauss. A TorusGeometry's RotateGeometryDecorator look-up does not apply (no decorators).
+// NetzerAccretionDiskGeometry.cpp, StellarSurfaceGeometry.cpp, SpheBackgroundGeometry.cpp, CubBackgroundGeometry.cpp,
+// SolarPatchGeometry.cpp and LaserGeometry.cpp: sources only (densities 0 or infinite), emitting anisotropically
+// (AngularDistribution); their positions, directions and probabilities are device/aniso_emission.hpp's, compiled here
+// for the host.
 enum class GeometryKind : int {
     Plummer = 0, ExpDisk = 1, Sersic = 2, Point = 3, Shell = 4, Gamma = 5, Gaussian = 6, TTauriDisk = 7, Torus = 8,
-    ConicalShell = 9
+    ConicalShell = 9, Netzer = 10, StellarSurface = 11, SpheBackground = 12, CubBackground = 13, SolarPatch = 14,
+    Laser = 15
 };
+inline bool isAnisotropic(GeometryKind k) { return (int)k >= (int)GeometryKind::Netzer; }
+// Geometry::dimension() of the anisotropic kinds (the others' is not looked at: loadSki)
+inline int anisoDimension(GeometryKind k) {
+    return k == GeometryKind::CubBackground ? 3
+           : (k == GeometryKind::StellarSurface || k == GeometryKind::SpheBackground) ? 1 : 2;
+}
 
 // SpecialFunctions::gln, gln2, gexp (SpecialFunctions.cpp:754-791)
 double gln(double p, double x);
@@ -57,6 +69,8 @@ struct Geometry {
     // Gamma: slope gamma (scale in b); Gaussian: dispersion sigma (flattening in q); TTauriDisk: radial scale Rd and
     // axial scale zd (inner and outer radius in rmin, rmax); rho0 above for the three
     double gamma = 0, sigma = 0, Rd = 0, zd = 0;
+    // StellarSurface, SpheBackground, SolarPatch: the radius; CubBackground: the extent (half-size)
+    double r0 = 0;
 
     double density(double x, double y, double z) const;
     double sersicInverseMass(double M) const;  // SersicFunction::inversemass
@@ -221,6 +235,12 @@ bool geometryPosition(const Geometry& g, R& rng, double& x, double& y, double& z
     case GeometryKind::TTauriDisk: ttauriPosition(g, rng, x, y, z); return true;
     case GeometryKind::Torus:
     case GeometryKind::ConicalShell: return torusPosition(g, rng, x, y, z);
+    case GeometryKind::Netzer:
+    case GeometryKind::StellarSurface:
+    case GeometryKind::SpheBackground:
+    case GeometryKind::CubBackground:
+    case GeometryKind::SolarPatch:
+    case GeometryKind::Laser: anisoPositionOf((int)g.kind, g.r0, rng, x, y, z); return true;
     case GeometryKind::Plummer: {
         // PlummerGeometry::randomradius, then SpheGeometry::generatePosition (Random::direction)
         const double t = std::pow(rng.uniform(), 1.0 / 3.0);

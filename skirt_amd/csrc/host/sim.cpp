@@ -114,9 +114,18 @@ int packGeometry(const Geometry& g, double* p) {
         for (int q = 0; q < 7; q++) p[q] = v[q];
         return g.kind == GeometryKind::Torus ? SKIRT_GEOM_TORUS : SKIRT_GEOM_CONICALSHELL;
     }
+    case GeometryKind::Netzer:
+    case GeometryKind::StellarSurface:
+    case GeometryKind::SpheBackground:
+    case GeometryKind::CubBackground:
+    case GeometryKind::SolarPatch:
+    case GeometryKind::Laser: p[0] = g.r0; return (int)g.kind;  // (SKIRT_GEOM_* are the kinds' values: asserted below)
     default: p[0] = g.c; p[1] = g.rho0; return SKIRT_GEOM_PLUMMER;
     }
 }
+static_assert((int)GeometryKind::Netzer == SKIRT_GEOM_NETZER && (int)GeometryKind::Laser == SKIRT_GEOM_LASER &&
+                  (int)GeometryKind::CubBackground == SKIRT_GEOM_CUBBACKGROUND,
+              "the anisotropic kinds of model.hpp are the C ABI's");
 // the first words of a TorusGeometry's or ConicalShellGeometry's row of geom_table / dens_table
 bool packGeometryTable(const Geometry& g, double* t) {
     if (g.kind != GeometryKind::Torus && g.kind != GeometryKind::ConicalShell) return false;
@@ -480,6 +489,71 @@ int skirt_sim_sample_positions(SkirtSim* s, int comp, int device, uint64_t seed,
             return SKIRT_ERR_NUMERIC;
         }
         if (draws) draws[i] = (int32_t)(2u * rng.block - (rng.have ? 1u : 0u));
+    }
+    return SKIRT_OK;
+}
+
+int skirt_sim_sample_launches(SkirtSim* s, int comp, int device, uint64_t seed, uint64_t first, size_t n, double* pos,
+                              double* dir, int32_t* draws, size_t nprob, const double* prob_pos, const double* prob_dir,
+                              double* prob) {
+    if (!s || (n && (!pos || !dir)) || (nprob && (!prob_dir || !prob))) return SKIRT_ERR_ARG;
+    if (comp < 0 || comp >= (int)s->m.starGeom.size()) {
+        g_err = "no stellar component " + std::to_string(comp);
+        return SKIRT_ERR_ARG;
+    }
+    if (nprob && !prob_pos && nprob > n) {
+        g_err = "more directions than launched positions";
+        return SKIRT_ERR_ARG;
+    }
+    if (device >= 0) {
+        if (!s->eng) { g_err = "no engine attached"; return SKIRT_ERR_STATE; }
+        if (device != s->device) {
+            g_err = "the engine is attached to device " + std::to_string(s->device) + ", not " + std::to_string(device);
+            return SKIRT_ERR_ARG;
+        }
+        return check(s, skirt_mcrt_sample_launches(s->eng, comp, seed, first, n, pos, dir, draws, nprob, prob_pos, prob_dir,
+                                                   prob));
+    }
+    const Geometry& g = s->m.starGeom[comp];
+    const bool aniso = isAnisotropic(g.kind);
+    // a position where the reference's functions throw, in its words, before anything runs
+    if (aniso && prob_pos)
+        for (size_t i = 0; i < nprob; i++) {
+            const double* p = prob_pos + 3 * i;
+            if (anisoPositionValid((int)g.kind, g.r0, p[0], p[1], p[2])) continue;
+            g_err = g.kind == GeometryKind::StellarSurface
+                        ? "the directional probability function is not defined for positions not on the stellar surface"
+                    : g.kind == GeometryKind::SpheBackground
+                        ? "the directional probability function is not defined for positions not on the background sphere"
+                    : g.kind == GeometryKind::CubBackground
+                        ? "the directional probability function is not defined for positions not on the background cube"
+                        : "the angular probability function is not defined for positions besides the origin";
+            return SKIRT_ERR_ARG;
+        }
+    // the host's compilation of the engine's routines (aniso_emission.hpp; the host's position templates and
+    // Random::direction for the isotropic kinds) on the engine's per-packet streams
+    std::vector<double> netzer;
+    if (g.kind == GeometryKind::Netzer) {
+        netzer.resize(anisoNetzerWords);
+        anisoNetzerTable(netzer.data());
+    }
+    for (size_t i = 0; i < n; i++) {
+        skirt_dev::PacketRng rng;
+        rng.start(seed, SKIRT_LAUNCHES_TAG, first + i);
+        double* p = pos + 3 * i;
+        double* k = dir + 3 * i;
+        if (!geometryPosition(g, rng, p[0], p[1], p[2])) {
+            g_err = "a TorusGeometry or ConicalShellGeometry found no position in 65536 attempts";
+            return SKIRT_ERR_NUMERIC;
+        }
+        if (aniso) anisoDirectionOf((int)g.kind, g.r0, netzer.data(), rng, p[0], p[1], p[2], k[0], k[1], k[2]);
+        else radialPosition(1.0, rng, k[0], k[1], k[2]);  // Random::direction()
+        if (draws) draws[i] = (int32_t)(2u * rng.block - (rng.have ? 1u : 0u));
+    }
+    for (size_t i = 0; i < nprob; i++) {
+        const double* p = prob_pos ? prob_pos + 3 * i : pos + 3 * i;
+        const double* k = prob_dir + 3 * i;
+        prob[i] = aniso ? anisoProbabilityOf((int)g.kind, g.r0, p[0], p[1], p[2], k[0], k[1], k[2]) : 1.0;
     }
     return SKIRT_OK;
 }
