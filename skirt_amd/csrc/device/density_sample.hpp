@@ -1,4 +1,4 @@
-// The setup's sampling kernels: DensArgs, geomDensity, samplePositionsKernel, sampleLaunchesKernel and
+// The setup's sampling kernels (DensArgs: engine_args.hpp): geomDensity, samplePositionsKernel, sampleLaunchesKernel and
 // densitySampleKernel. Compiles only where engine.hip includes it, inside its anonymous namespace, after Events
 // (Events::launchPosition, launchDirection, emissionProbability).
 #ifndef SKIRT_AMD_DEVICE_DENSITY_SAMPLE_HPP
@@ -10,18 +10,6 @@
 // densities and tree subdivision). The geometry densities follow the host's Geometry::density operation
 // for operation (PlummerGeometry.cpp:49-54, ExpDiskGeometry::density, SersicGeometry::density with the
 // SersicFunction log-log interpolation, PointGeometry).
-struct DensArgs {
-    int ncomp, ntab, nsample, mode;
-    const int* kind;
-    const double* param;  // ncomp x 8
-    const double* norm;   // ncomp
-    const double* table;  // ncomp x 2 ntab
-    const double* boxes;  // n x 6
-    const uint32_t* words;
-    double* out;
-    size_t n;
-};
-
 __device__ double geomDensity(const DensArgs& d, int h, double x, double y, double z) {
     const double* p = d.param + 8 * h;
     switch (d.kind[h]) {

@@ -1,5 +1,5 @@
-// Dust emission sources on the device: EmisArgs, the cell-spectra, scan, CDF and guide kernels, and the
-// guided table lookups the event side draws cells with.
+// Dust emission sources on the device (their arguments: EmisArgs, engine_args.hpp): the cell-spectra, scan, CDF and
+// guide kernels, and the guided table lookups the event side draws cells with.
 // Compiles only where engine.hip includes it, inside its anonymous namespace.
 #ifndef SKIRT_AMD_DEVICE_EMISSION_HPP
 #define SKIRT_AMD_DEVICE_EMISSION_HPP
@@ -11,28 +11,6 @@
 // NR::cdf of PanMonteCarloSimulation.cpp:193-205, 273-294), computed from the device tallies so the
 // self-absorption cycles never leave the GPU. Reference cell order, like the host restatement
 // (host/dustemission.cpp), which the tests compare against.
-struct EmisArgs {
-    int ncells, nlambda, ncomp, ntemp;
-    const int* devCell;          // reference cell -> device cell (null: identity)
-    const double* labs;          // [nlambda][device cell]
-    const double* labsDust;      // same, or null
-    const double* rho;           // [device cell][ncomp]
-    const double* volume;        // [reference cell]
-    const double* kabs;          // [ncomp][nlambda]
-    const double* sigmaabs;      // [ncomp][nlambda]
-    const double* mu;            // [ncomp]
-    const double* Tv;            // [ntemp]
-    const double* planckabs;     // [ncomp][ntemp]
-    const double* lambda;        // [nlambda]
-    const double* dlambda;       // [nlambda]
-    int labsStride;              // Labs row length
-    double* lv;                  // out [nlambda][ncells]
-    double* cdf;                 // out [nlambda][ncells + 1]
-    double* ltot;                // out [nlambda]
-    double* blockSums;           // scratch [nlambda][nblocks]
-    int nblocks;
-};
-
 __device__ __forceinline__ double planckB(double T, double lambda) {  // PlanckFunction
     const double h = 6.62606957e-34, c = 2.99792458e8, k = 1.3806488e-23;
     const double x = h * c / (lambda * k * T);

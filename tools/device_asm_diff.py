@@ -7,11 +7,16 @@
 
 A change that only moves source text must leave every function's instructions as they were. The compiler
 numbers functions in the order it emits them, and that number appears in local labels (.LBB<n>_<m>,
-.Lfunc_end<n>), so those numbers are masked, and assembler comments are dropped. Prints every symbol whose
+.Lfunc_end<n>), so those numbers are masked, and assembler comments are dropped. A type that moves to another
+namespace changes the mangled name of every function taking it, so functions are keyed by their demangled
+name with the namespace qualifiers stripped (llvm-cxxfilt or c++filt), and inside a body every symbol of the
+listing is written as its key. Prints every symbol whose
 text differs (or that one side lacks) with its instruction count and, for kernels, the registers and
 scratch bytes of both sides. Exit status 1 if any symbol differs, else 0.
 """
 import re
+import shutil
+import subprocess
 import sys
 
 TYPE = re.compile(r"^\s*\.type\s+([^,\s]+),@function")
@@ -21,8 +26,32 @@ FIGURES = ("next_free_vgpr", "accum_offset", "private_segment_fixed_size")
 FIGURE = re.compile(r"^\.amdhsa_(%s)\s+(\S+)" % "|".join(FIGURES))
 
 
+MANGLED = re.compile(r"\b_Z\w+")
+QUALIFIER = re.compile(r"(?:\(anonymous namespace\)|[A-Za-z_]\w*)::")
+
+
+def keys(names):
+    """{symbol: demangled name without namespace qualifiers}; the symbol itself where it does not demangle"""
+    tool = shutil.which("llvm-cxxfilt") or shutil.which("llvm-cxxfilt", path="/opt/rocm/llvm/bin:/opt/rocm/lib/llvm/bin") \
+        or shutil.which("c++filt")
+    if not tool:
+        sys.exit("device_asm_diff.py needs llvm-cxxfilt or c++filt")
+    names = list(names)
+    plain = subprocess.run([tool], input="\n".join(names) + "\n", capture_output=True, text=True, check=True).stdout
+    return {n: QUALIFIER.sub("", d) for n, d in zip(names, plain.split("\n"))}
+
+
 def symbols(path):
-    """{symbol: (normalized lines, instruction count, {figure: value})} of one listing"""
+    """{key: (normalized lines, instruction count, {figure: value})} of one listing"""
+    raw = raw_symbols(path)
+    key = keys(raw)
+    if len(set(key.values())) != len(key):
+        sys.exit("%s: two symbols with one key" % path)
+    return {key[n]: ([MANGLED.sub(lambda k: key.get(k.group(0), k.group(0)), l) for l in lines], instr, fig)
+            for n, (lines, instr, fig) in raw.items()}
+
+
+def raw_symbols(path):
     out = {}
     name, body, descriptor = None, None, False
     for raw in open(path, errors="replace"):

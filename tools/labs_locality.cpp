@@ -2,7 +2,7 @@
 // would the trace kernel issue for one launch's FILL rays under different ray orders and merge schemes?
 //
 // The FILL paths come from the oracle (Philox streams, the engine's packets) through oracle_set_fill_hook;
-// cells are renumbered as the engine numbers device cells (numberTreeLeaves on engine.hip's host side:
+// cells are renumbered as the engine numbers device cells (numberTreeLeaves of host/engine_layout.cpp:
 // depth-first octant order, groups of 8 sibling leaves aligned to one 64-byte line of a Labs row). Then a model of the persistent trace kernel
 // (W waves of 64 lanes, one segment per lane-step, 64-ray pull chunks handed round robin to the waves,
 // kLabsBuf = 16 adds buffered per lane) counts requests for:
@@ -31,6 +31,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "engine_layout.cpp"  // numberTreeLeaves: the engine's own numbering, compiled into this tool
 #include "model.hpp"
 #include "oracle.h"
 
@@ -60,26 +61,21 @@ void hook(void* user, int ell, const double r[3], const double k[3], const int* 
     s->rays.push_back(y);
 }
 
-// the engine's octree device numbering (numberTreeLeaves in engine.hip's host side, upload of SKIRT_GRID_OCTREE)
+// the engine's octree device numbering: numberTreeLeaves itself (host/engine_layout.cpp)
 std::vector<int> deviceCells(const skirt::OctreeGrid& g, int ncells) {
-    std::vector<int> dev(ncells, -1);
-    std::vector<int> stack{0};
-    int next = 0;
-    while (!stack.empty()) {
-        const int l = stack.back();
-        stack.pop_back();
-        const int fc = g.firstChild[l];
-        if (fc < 0) { dev[g.cellnumber[l]] = next++; continue; }
-        bool leaves = true;
-        for (int k = 0; k < 8 && leaves; k++) leaves = g.firstChild[fc + k] < 0;
-        if (leaves) {
-            next = (next + 7) & ~7;
-            for (int k = 0; k < 8; k++) dev[g.cellnumber[fc + k]] = next++;
-        } else {
-            for (int k = 7; k >= 0; k--) stack.push_back(fc + k);
-        }
+    SkirtGridDesc d{};
+    d.kind = SKIRT_GRID_OCTREE;
+    d.ncells = ncells;
+    d.nnodes = (int)g.firstChild.size();
+    d.first_child = g.firstChild.data();
+    d.cellnumber = g.cellnumber.data();
+    skirt_dev::CellNumbering num;
+    std::string err;
+    if (skirt_dev::numberTreeLeaves(&d, num, err)) {
+        fprintf(stderr, "numberTreeLeaves: %s\n", err.c_str());
+        exit(1);
     }
-    return dev;
+    return num.devCell;
 }
 
 struct Result {

@@ -12,11 +12,14 @@
 // up / down, mode r~ each one by a pseudo-random -1, 0 or +1 ulp, so that the margin the device relies on
 // is what the walk checks.
 #include "../skirt_amd/csrc/device/vor_terms.hpp"
+#include "../skirt_amd/csrc/host/engine_layout.cpp"  // packVoronoi: the engine's own packing, compiled into this tool
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <random>
 #include <vector>
 
@@ -269,8 +272,7 @@ int main(int argc, char** argv) {
     for (int m = 0; m < N; m++)
         if (g.cell_nbr_offset[m + 1] - g.cell_nbr_offset[m] > 4096) { fprintf(stderr, "neighbour list too long\n"); return 1; }
     M.off.assign(3 * (size_t)nn, 0.f);
-    // scaled float offsets as the device stores them (engine.hip's host side, uploadVoronoi): walls as the offset to
-    // the site's mirror image
+    // scaled float offsets n (the modes before r): walls as the offset to the site's mirror image
     for (int m = 0; m < N; m++)
         for (int q = g.cell_nbr_offset[m]; q < g.cell_nbr_offset[m + 1]; q++) {
             const int mi = g.cell_nbr_list[q];
@@ -281,31 +283,39 @@ int main(int argc, char** argv) {
                 const double w = lim - sm[axis];
                 for (int d = 0; d < 3; d++) M.off[3 * (size_t)q + d] = 0.f;
                 M.off[3 * (size_t)q + axis] = w != 0.0 ? (float)(2.0 * w * gScale) : 0.0f;  // degenerate: n = 0, den = 0, sign uncertain
-                if (gRecip) {  // as the engine's Voronoi upload: m = n / |n|^2 (vor_terms.hpp)
-                    double n[3] = {0.0, 0.0, 0.0};
-                    n[axis] = w != 0.0 ? 2.0 * w * gScale : NAN;
-                    vorRecipOffset(n[0], n[1], n[2], &M.off[3 * (size_t)q]);
-                }
                 continue;
             }
             for (int d = 0; d < 3; d++) M.off[3 * (size_t)q + d] = (float)((g.site[3 * (size_t)mi + d] - sm[d]) * gScale);
-            if (gRecip)
-                vorRecipOffset((g.site[3 * (size_t)mi] - sm[0]) * (double)gScale, (g.site[3 * (size_t)mi + 1] - sm[1]) * (double)gScale,
-                               (g.site[3 * (size_t)mi + 2] - sm[2]) * (double)gScale, &M.off[3 * (size_t)q]);
         }
+    // mode r: the reciprocal entries m = n / |n|^2 and the cells' error terms exactly as the device holds them,
+    // decoded from the engine's own packing (packVoronoi, host/engine_layout.cpp)
+    M.eA.assign(N, 0.f);
+    M.eB.assign(N, 0.f);
+    if (gRecip) {
+        skirt_dev::VoronoiPack pack;
+        std::string err;
+        if (skirt_dev::packVoronoi(&g, pack, err)) { fprintf(stderr, "packVoronoi: %s\n", err.c_str()); return 1; }
+        for (int m = 0; m < N; m++) {
+            const skirt_dev::VorEntry* blk = pack.slots.data() + pack.start[pack.devCell[m]];
+            int o = 0;
+            for (int q = g.cell_nbr_offset[m]; q < g.cell_nbr_offset[m + 1]; q++, o++) {
+                const float* P = reinterpret_cast<const float*>(blk + skirt_dev::kVorHead + (o & ~1));
+                for (int d = 0; d < 3; d++) M.off[3 * (size_t)q + d] = P[2 * d + (o & 1)];
+            }
+            memcpy(&M.eA[m], reinterpret_cast<const char*>(blk + 2) + 8, 4);
+            memcpy(&M.eB[m], reinterpret_cast<const char*>(blk + 2) + 12, 4);
+        }
+    }
     M.nmax.assign(N, 0.f);
     for (int m = 0; m < N; m++)
         for (int q = g.cell_nbr_offset[m]; q < g.cell_nbr_offset[m + 1]; q++) {
             const float x = M.off[3 * (size_t)q], y = M.off[3 * (size_t)q + 1], z = M.off[3 * (size_t)q + 2];
             M.nmax[m] = fmaxf(M.nmax[m], sqrtf(x * x + y * y + z * z) * (1.0f + 4 * FLT_EPSILON));
         }
-    // the header's per-cell error terms as the engine's Voronoi upload computes them
-    M.eA.assign(N, 0.f);
-    M.eB.assign(N, 0.f);
-    for (int m = 0; m < N; m++) {
+    // the other modes' per-cell error terms
+    for (int m = 0; m < N && !gRecip; m++) {
         const int q0 = g.cell_nbr_offset[m], q1 = g.cell_nbr_offset[m + 1];
-        if (gRecip) vorRecipErrorTerms(M.off.data() + 3 * (size_t)q0, q1 - q0, 3, &M.eA[m], &M.eB[m]);
-        else vorErrorTerms(M.off.data() + 3 * (size_t)q0, q1 - q0, 3, &M.eA[m], &M.eB[m]);
+        vorErrorTerms(M.off.data() + 3 * (size_t)q0, q1 - q0, 3, &M.eA[m], &M.eB[m]);
     }
     long steps = 0, fallbacks = 0, mismatches = 0;
     for (int i = 0; i < R; i++) {
