@@ -6,9 +6,9 @@
 
 // ================================================================== setup: density sampling
 // The setup's hot loop (skirt_mcrt_sample_density): one thread per item (a cell or a tree node), its
-// samples in order, so that every sum is accumulated as the host loop accumulates it (build.cpp cell
-// densities and tree subdivision). The geometry densities follow the host's Geometry::density operation
-// for operation (PlummerGeometry.cpp:49-54, ExpDiskGeometry::density, SersicGeometry::density with the
+// samples in order, so that every sum is accumulated as the host loop accumulates it (host/densities.cpp cell
+// densities, host/treegrid.cpp tree subdivision). The geometry densities follow the host's Geometry::density
+// operation for operation (PlummerGeometry.cpp:49-54, ExpDiskGeometry::density, SersicGeometry::density with the
 // SersicFunction log-log interpolation, PointGeometry).
 __device__ double geomDensity(const DensArgs& d, int h, double x, double y, double z) {
     const double* p = d.param + 8 * h;

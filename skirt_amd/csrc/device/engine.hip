@@ -1015,7 +1015,7 @@ struct Events {
     }
 
     // SpecialFunctions::LambertW1 (SpecialFunctions.cpp:579-626), the W_{-1} branch; as the host's
-    // lambertW1 (host/build.cpp), whose argument checks the callers here never fail
+    // lambertW1 (host/geometry.cpp), whose argument checks the callers here never fail
     __device__ static double lambertW1(double z) {
         const double eps = 1.0e-12;
         const double em1 = 0.3678794411714423215955237701614608;

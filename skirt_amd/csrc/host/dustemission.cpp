@@ -1,5 +1,6 @@
 // Dust emission spectra and dust-phase cell sources; see dustemission.hpp for the reference map.
 #include "dustemission.hpp"
+#include "nr.hpp"
 
 #include <cmath>
 #include <stdexcept>
@@ -12,30 +13,13 @@ constexpr double kH = 6.62606957e-34;  // Units.cpp:17-19
 constexpr double kC = 2.99792458e8;
 constexpr double kK = 1.3806488e-23;
 
-// NR::locate_clip (NR.hpp): index j with xv[j] <= x < xv[j+1], clipped to [0, n-2]
-int locateClip(const double* xv, int n, double x) {
-    if (x < xv[0]) return 0;
-    int jl = -1, ju = n - 1;
-    while (ju - jl > 1) {
-        int jm = (ju + jl) >> 1;
-        if (x < xv[jm]) ju = jm;
-        else jl = jm;
-    }
-    return jl;
-}
-
-double interpolateLinLin(double x, double x1, double x2, double f1, double f2) {
-    return f1 + ((x - x1) / (x2 - x1)) * (f2 - f1);
-}
-
 // DustMix::equilibrium (DustMix.cpp:704-712) for a one-population mix
 double equilibrium(const DustMix& mix, const PlanckTable& t, const WavelengthGrid& wl, const std::vector<double>& Jv) {
     double planckabs = 0.0;
     for (int ell = 0; ell < wl.n(); ell++) planckabs += mix.sigmaabs[ell] * Jv[ell] * wl.dlambda[ell];
     // DustMix::invplanckabs (DustMix.cpp:689-693)
-    int n = (int)t.planckabs.size();
-    int p = locateClip(t.planckabs.data(), n, planckabs);
-    return interpolateLinLin(planckabs, t.planckabs[p], t.planckabs[p + 1], t.Tv[p], t.Tv[p + 1]);
+    int p = nr::locateClip(t.planckabs, planckabs);
+    return nr::interpolateLinLin(planckabs, t.planckabs[p], t.planckabs[p + 1], t.Tv[p], t.Tv[p + 1]);
 }
 
 // GreyBodyDustEmissivity::emissivity (GreyBodyDustEmissivity.cpp:19-43), one population

@@ -2,8 +2,11 @@
 //
 // The reference spreads this state over its SimulationItem tree (MonteCarloSimulation, StellarSystem,
 // DustSystem, DustGrid, DustMix, Instrument subclasses). Here it is one plain struct of flat arrays,
-// built once on the host (build.cpp) and then handed to the device engine through the C ABI
-// (include/skirt_mcrt.h) or to the CPU checker in oracle/.
+// built once on the host and then handed to the device engine through the C ABI (include/skirt_mcrt.h) or to
+// the CPU checker in oracle/. loadSki (build.cpp) drives the set-up, one file per subject: geometry.cpp (the
+// Geometry members, the special functions, the geometry parsers), sources.cpp (wavelength grids, SEDs, the stellar
+// system), dustmix.cpp, dustgrid.cpp (the grids' members and parsers), treegrid.cpp (the tree builder) and
+// densities.cpp (the cell densities), with nr.hpp, workers.hpp and the internal ski_parse.hpp.
 #pragma once
 
 #include <cmath>
@@ -48,10 +51,12 @@ inline int anisoDimension(GeometryKind k) {
            : (k == GeometryKind::StellarSurface || k == GeometryKind::SpheBackground) ? 1 : 2;
 }
 
-// SpecialFunctions::gln, gln2, gexp (SpecialFunctions.cpp:754-791)
+// geometry.cpp: SpecialFunctions::gln, gln2, gexp (SpecialFunctions.cpp:754-791) and LambertW1
+// (SpecialFunctions.cpp:579-626, the W_{-1} branch), which the position templates below call
 double gln(double p, double x);
 double gln2(double p, double x1, double x2);
 double gexp(double p, double x);
+double lambertW1(double z);
 
 struct Geometry {
     GeometryKind kind = GeometryKind::Plummer;
@@ -81,9 +86,6 @@ struct Geometry {
     double Sigmar() const;
 };
 
-// SpecialFunctions::LambertW1 (SKIRTcore/SpecialFunctions.cpp:579-626): the W_{-1} branch
-double lambertW1(double z);
-
 // ExpDiskGeometry::randomR / randomz and SepAxGeometry::generatePosition, in the reference's draw order
 template <class R>
 void expDiskPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
@@ -103,21 +105,31 @@ void expDiskPosition(const Geometry& g, R& rng, double& x, double& y, double& z)
     z = zc;
 }
 
-// SersicGeometry::randomradius then SpheGeometry::generatePosition: Random::direction() as
-// Direction(theta, phi) with theta = acos(2u-1), phi = 2 pi u' (Random.cpp:179-184, Direction.cpp)
-template <class R>
-void sersicPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
-    const double r = g.reff * g.sersicInverseMass(rng.uniform());
-    const double theta = std::acos(2.0 * rng.uniform() - 1.0);
-    const double phi = 2.0 * M_PI * rng.uniform();
-    double kx, ky, kz;
+// Direction(theta, phi) (Direction.cpp): the unit vector, the poles within 1e-8 exactly on the axis
+inline void direction(double theta, double phi, double& kx, double& ky, double& kz) {
     if (theta <= 1e-8) { kx = 0; ky = 0; kz = 1; }
     else if (theta >= M_PI - 1e-8) { kx = 0; ky = 0; kz = -1; }
     else {
         const double st = std::sin(theta);
         kx = st * std::cos(phi); ky = st * std::sin(phi); kz = std::cos(theta);
     }
+}
+
+// SpheGeometry::generatePosition after randomradius: Position(r, Random::direction()), Random::direction() as
+// Direction(theta, phi) with theta = acos(2u-1), phi = 2 pi u' (Random.cpp:179-184)
+template <class R>
+void radialPosition(double r, R& rng, double& x, double& y, double& z) {
+    const double theta = std::acos(2.0 * rng.uniform() - 1.0);
+    const double phi = 2.0 * M_PI * rng.uniform();
+    double kx, ky, kz;
+    direction(theta, phi, kx, ky, kz);
     x = r * kx; y = r * ky; z = r * kz;
+}
+
+// SersicGeometry::randomradius then SpheGeometry::generatePosition
+template <class R>
+void sersicPosition(const Geometry& g, R& rng, double& x, double& y, double& z) {
+    radialPosition(g.reff * g.sersicInverseMass(rng.uniform()), rng, x, y, z);
 }
 
 // Random::gauss (Random.cpp:140-150)
@@ -130,21 +142,6 @@ double gaussDeviate(R& rng) {
         rsq = v1 * v1 + v2 * v2;
     } while (rsq >= 1.0 || rsq == 0.0);
     return v2 * std::sqrt(-2.0 * std::log(rsq) / rsq);
-}
-
-// SpheGeometry::generatePosition after randomradius: Position(r, Random::direction())
-template <class R>
-void radialPosition(double r, R& rng, double& x, double& y, double& z) {
-    const double theta = std::acos(2.0 * rng.uniform() - 1.0);
-    const double phi = 2.0 * M_PI * rng.uniform();
-    double kx, ky, kz;
-    if (theta <= 1e-8) { kx = 0; ky = 0; kz = 1; }
-    else if (theta >= M_PI - 1e-8) { kx = 0; ky = 0; kz = -1; }
-    else {
-        const double st = std::sin(theta);
-        kx = st * std::cos(phi); ky = st * std::sin(phi); kz = std::cos(theta);
-    }
-    x = r * kx; y = r * ky; z = r * kz;
 }
 
 // ShellGeometry::randomradius
@@ -284,11 +281,31 @@ struct DustComp {
     double density(double x, double y, double z) const { return nf * geom.density(x, y, z); }
 };
 
+// The grids of every kind, each with its cells' geometry read together (dustgrid.cpp): the box or the volume and
+// central position, whichcell, and positionInCell(m), which returns the random position in cell m as a function
+// of three uniform deviates, (const double u[3], double p[3]), in the reference's arithmetic. These members are the
+// library's own (SKIRT_LOCAL: not among its dynamic symbols); DustGrid's four methods below are what other code calls.
+#define SKIRT_LOCAL __attribute__((visibility("hidden")))
+
+// Random::position(box) then Box::fracpos: the position at the fractions u of a box's extent
+inline void boxPosition(const double b[6], const double u[3], double p[3]) {
+    p[0] = b[0] + u[0] * (b[3] - b[0]);
+    p[1] = b[1] + u[1] * (b[4] - b[1]);
+    p[2] = b[2] + u[2] * (b[5] - b[2]);
+}
+struct BoxPosition {
+    double b[6];
+    void operator()(const double u[3], double p[3]) const { boxPosition(b, u, p); }
+};
+
 // Cartesian grid: SKIRTcore/CartesianDustGrid.cpp
 struct CartesianGrid {
     int Nx = 0, Ny = 0, Nz = 0;
     double xmin = 0, xmax = 0, ymin = 0, ymax = 0, zmin = 0, zmax = 0;
     std::vector<double> xv, yv, zv;  // N+1 borders each
+    SKIRT_LOCAL void cellBox(int m, double b[6]) const;
+    SKIRT_LOCAL int whichcell(double x, double y, double z) const;
+    SKIRT_LOCAL BoxPosition positionInCell(int m) const;
 };
 
 // Tree grids: SKIRTcore/TreeDustGrid.cpp with OctTreeNode.cpp / BaryOctTreeNode.cpp (OctTreeDustGrid) or
@@ -323,6 +340,9 @@ struct OctreeGrid {
         }
         return c0 + (x < cb[3] ? 0 : 1) + (y < cb[4] ? 0 : 2) + (z < cb[5] ? 0 : 4);
     }
+    SKIRT_LOCAL void cellBox(int m, double b[6]) const;  // of cell m (not node m)
+    SKIRT_LOCAL int whichcell(double x, double y, double z) const;
+    SKIRT_LOCAL BoxPosition positionInCell(int m) const;
 };
 
 // Axisymmetric R-z grid: SKIRTcore/Cylinder2DDustGrid.cpp (CylinderDustGrid.cpp); cell m = k + Nz*i
@@ -330,6 +350,20 @@ struct Cylinder2DGrid {
     int NR = 0, Nz = 0;
     double Rmax = 0, zmin = 0, zmax = 0;
     std::vector<double> Rv, zv;  // NR+1 radial borders (Rv[0] = 0), Nz+1 z borders
+    // Cylinder2DDustGrid::randomPositionInCell: three deviates (R, phi, z)
+    struct Position {
+        double R0, R1, z0, z1;
+        void operator()(const double u[3], double p[3]) const {
+            const double R = R0 + (R1 - R0) * u[0];
+            const double phi = 2.0 * M_PI * u[1];
+            const double z = z0 + (z1 - z0) * u[2];
+            p[0] = R * std::cos(phi); p[1] = R * std::sin(phi); p[2] = z;
+        }
+    };
+    SKIRT_LOCAL double volume(int m) const;
+    SKIRT_LOCAL void center(int m, double c[3]) const;
+    SKIRT_LOCAL int whichcell(double x, double y, double z) const;
+    SKIRT_LOCAL Position positionInCell(int m) const;
 };
 
 // Spherical grids: SKIRTcore/Sphere1DDustGrid.cpp (shells, cell m = i) and Sphere2DDustGrid.cpp (shells x polar
@@ -340,6 +374,38 @@ struct SphereGrid {
     std::vector<double> rv;      // Nr+1 radial borders (mesh * rmax; a LogMesh's last may miss rmax by a bit)
     std::vector<double> thetav;  // 2D: Ntheta+1 polar borders, a border pi/2 inserted where the mesh has none
     std::vector<double> cv;      // 2D: their cosines, with exact 1, 0, -1 (Sphere2DDustGrid::setupSelfAfter)
+    // Sphere1DDustGrid::randomPositionInCell: Random::direction() (theta, phi), then r uniform in the shell
+    struct Position1D {
+        double r0, r1;
+        void operator()(const double u[3], double p[3]) const {
+            const double theta = std::acos(2.0 * u[0] - 1.0);
+            const double phi = 2.0 * M_PI * u[1];
+            double kx, ky, kz;
+            direction(theta, phi, kx, ky, kz);
+            const double r = r0 + (r1 - r0) * u[2];
+            p[0] = r * kx; p[1] = r * ky; p[2] = r * kz;
+        }
+    };
+    // Sphere2DDustGrid::randomPositionInCell: r, theta, phi, then Position(.., SPHERICAL)
+    struct Position2D {
+        double ris, ri1s, theta0, theta1;  // the squares of the shell's radii, the polar bin's borders
+        void operator()(const double u[3], double p[3]) const {
+            const double r = std::sqrt(ris + (ri1s - ris) * u[0]);
+            const double theta = theta0 + (theta1 - theta0) * u[1];
+            const double phi = 2.0 * M_PI * u[2];
+            const double costheta = std::cos(theta), sintheta = std::sin(theta);
+            const double cosphi = std::cos(phi), sinphi = std::sin(phi);
+            p[0] = r * sintheta * cosphi; p[1] = r * sintheta * sinphi; p[2] = r * costheta;
+        }
+    };
+    SKIRT_LOCAL double volume1D(int m) const;
+    SKIRT_LOCAL double volume2D(int m) const;
+    SKIRT_LOCAL void center1D(int m, double c[3]) const;
+    SKIRT_LOCAL void center2D(int m, double c[3]) const;
+    SKIRT_LOCAL int whichcell1D(double x, double y, double z) const;
+    SKIRT_LOCAL int whichcell2D(double x, double y, double z) const;
+    SKIRT_LOCAL Position1D positionInCell1D(int m) const;
+    SKIRT_LOCAL Position2D positionInCell2D(int m) const;
 };
 
 enum class GridKind : int { Cartesian = 0, Octree = 1, Voronoi = 2, Cylinder2D = 3, Sphere1D = 4, Sphere2D = 5 };
