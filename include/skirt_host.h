@@ -44,7 +44,27 @@ SkirtSim* skirt_sim_load(const char* ski, const char* datadir, double packages, 
  * draws the reference's random numbers and takes the subdivision decisions; densities may differ from the
  * host's by an ulp (the device's exp/pow/log10). -1: on the host, bit-identical to the reference. */
 SkirtSim* skirt_sim_load_ex(const char* ski, const char* datadir, double packages, uint64_t seed, int setup_device);
+/* As skirt_sim_load_ex; input_path is the folder where a relative file name of the model (the particle file of an
+ * SPHDustDistribution) is looked up, as the reference's -i option. NULL or "": the .ski file's own folder. With
+ * particle dust, setup_device >= 0 also runs the tree subdivision and the tree's cell densities by mass in box on
+ * the device (skirt_mcrt_particles_mass_in_box; boxes beyond its merge cap on host worker threads beside it) and the
+ * sampled densities of Cartesian, tree and Voronoi grids (skirt_mcrt_particles_sample), all equal to the host's
+ * bit for bit. */
+SkirtSim* skirt_sim_load_in(const char* ski, const char* datadir, double packages, uint64_t seed, int setup_device,
+                            const char* input_path);
 int skirt_sim_info(SkirtSim* sim, SkirtSimInfo* info);
+/* Imported particle dust (SPHDustDistribution). skirt_sim_particle_info: the number of particles kept, the number
+ * ignored for their temperature, whether the distribution offers massInBox to the grids (no negative mass) and the
+ * 3 x 21 separators of its cell grid (x, y, z; any pointer may be NULL); SKIRT_ERR_ARG for a model without
+ * particle dust. skirt_sim_particle_density: SPHDustDistribution::density at n points (3 doubles each);
+ * skirt_sim_particle_mass_in_box: massInBox of n boxes (6 doubles each: min xyz, max xyz), *handed_back (may be
+ * NULL) the number of boxes a device left to the host. device < 0: the host's functions; else that HIP device
+ * (the particle set is uploaded once per simulation and device). */
+int skirt_host_particle_merge_cap(void);  /* the cells of the particle grid a box may span on a device (64) */
+int skirt_sim_particle_info(SkirtSim* sim, int* nparticles, int* nignored, int* mass_interface, double* separators);
+int skirt_sim_particle_density(SkirtSim* sim, int device, size_t n, const double* points, double* out);
+int skirt_sim_particle_mass_in_box(SkirtSim* sim, int device, size_t n, const double* boxes, double* out,
+                                   size_t* handed_back);
 /* The seed of the photon phases' Philox streams (default: the setup seed). The grid, densities and every
  * other setup draw stay those of the setup seed, so runs that differ only in this seed are independent
  * Monte Carlo realisations on one and the same grid (per-cell statistics against a reference run). */

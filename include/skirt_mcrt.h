@@ -36,7 +36,10 @@ extern "C" {
 #endif
 
 #define SKIRT_MCRT_ABI_VERSION 14  /* 11: SkirtStats::packages; 12: SkirtStats::labs_cache_sets; 13: without it;
-                                     14: skirt_mcrt_voronoi_cells */
+                                     14: skirt_mcrt_voronoi_cells. The number stands for the layout of the
+                                     structs and the signatures of the functions there were at 14: functions and
+                                     structs added since (skirt_mcrt_particles_*, SkirtParticlesDesc) change neither
+                                     and do not bump it; a caller that needs them checks for the symbol */
 
 enum {
     SKIRT_OK = 0,
@@ -333,6 +336,37 @@ typedef struct {
 } SkirtDensityDesc;
 int skirt_mcrt_sample_density(int device, const SkirtDensityDesc* dens, const double* boxes, size_t n,
                               const uint32_t* words, int nsample, int mode, double* out);
+
+/* Setup: imported particle dust on a device (SPHDustDistribution; no engine context needed). A particle set is
+ * uploaded once: per particle eight doubles (centre x y z, then SPHGasParticle's _norm, _rho0, _rho2, _s, _MZ8 as the
+ * host cached them), the 3 x 21 separators of the 20 x 20 x 20 cell grid (x, y, z), the cells' particle lists as
+ * CSR (cell ((i*20)+j)*20+k; 8001 offsets; every list in ascending particle index) and the 5001-entry table
+ * erf(i * 2.5 / 5000) built on the host with the C library's erf. The upload checks every offset and index.
+ *   skirt_mcrt_particles_sample: skirt_mcrt_sample_density's two modes with the particle density as the one
+ *     component (SKIRT_DENS_COMPONENTS: out[n]; SKIRT_DENS_NODE: out[n x 6]); mode SKIRT_PART_POINTS takes `boxes`
+ *     as n points (three doubles each), no words, and gives out[n], the density at each.
+ *   skirt_mcrt_particles_mass_in_box: out[n], SPHDustDistribution::massInBox of each box (six doubles: min xyz, max
+ *     xyz). A box that spans more than 64 cells of the particle grid is not computed: out is -1 (no mass is
+ *     negative) and *handed_back (may be NULL) counts those boxes; the caller computes them on the host.
+ * The arithmetic is +, -, *, sqrt, comparisons, one truncation and table loads in the host's order (no FMA
+ * contraction on either side), so every output equals the host's bit for bit. Synchronous. */
+enum { SKIRT_PART_POINTS = 2 };
+typedef struct {
+    int nparticles;
+    const double* rec;          /* nparticles x 8 */
+    const double* separators;   /* 3 x 21 */
+    const int* cell_offset;     /* 8001 */
+    const int* cell_list;       /* cell_offset[8000] */
+    const double* erf_table;    /* 5001 */
+    double dust_fraction;
+} SkirtParticlesDesc;
+typedef struct SkirtParticles SkirtParticles;
+int skirt_mcrt_particles_upload(int device, const SkirtParticlesDesc* desc, SkirtParticles** out);
+int skirt_mcrt_particles_sample(SkirtParticles* p, const double* boxes, size_t n, const uint32_t* words, int nsample,
+                                int mode, double* out);
+int skirt_mcrt_particles_mass_in_box(SkirtParticles* p, const double* boxes, size_t n, double* out,
+                                     size_t* handed_back);
+void skirt_mcrt_particles_free(SkirtParticles* p);
 
 /* Geometry::generatePosition of source component `comp` of the uploaded sources, as the event kernel's launch
  * runs it: packet first + i draws from a fresh stream PacketRng::start(seed, SKIRT_POSITIONS_TAG, first + i)

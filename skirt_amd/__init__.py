@@ -82,6 +82,9 @@ ABI_SYMBOLS = [
     "skirt_mcrt_set_mueller", "skirt_mcrt_scatterings", "skirt_sim_polarization", "skirt_sim_scatterings",
     "skirt_host_write_mueller",
     "skirt_mcrt_sample_launches", "skirt_sim_sample_launches",
+    "skirt_mcrt_particles_upload", "skirt_mcrt_particles_sample", "skirt_mcrt_particles_mass_in_box",
+    "skirt_mcrt_particles_free", "skirt_sim_load_in", "skirt_sim_particle_info", "skirt_sim_particle_density",
+    "skirt_sim_particle_mass_in_box", "skirt_host_particle_merge_cap",
 ]
 
 _lib = None
@@ -153,6 +156,14 @@ def lib():
             L.skirt_sim_scatterings.argtypes = [vp, c_int, c_int, ctypes.c_size_t] + [ctypes.POINTER(c_dbl)] * 3
             L.skirt_mcrt_scatterings.argtypes = [vp, c_int, ctypes.c_size_t] + [ctypes.POINTER(c_dbl)] * 3
             L.skirt_mcrt_set_mueller.argtypes = [vp, vp]
+        if hasattr(L, "skirt_sim_load_in"):  # (likewise)
+            dp = ctypes.POINTER(c_dbl)
+            L.skirt_sim_load_in.restype = vp
+            L.skirt_sim_load_in.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_dbl, c_u64, c_int, ctypes.c_char_p]
+            L.skirt_sim_particle_info.argtypes = [vp] + [ctypes.POINTER(c_int)] * 3 + [dp]
+            L.skirt_sim_particle_density.argtypes = [vp, c_int, ctypes.c_size_t, dp, dp]
+            L.skirt_sim_particle_mass_in_box.argtypes = [vp, c_int, ctypes.c_size_t, dp, dp,
+                                                         ctypes.POINTER(ctypes.c_size_t)]
         L.skirt_sim_error.restype = ctypes.c_char_p
         L.skirt_sim_free.argtypes = [vp]
         L.skirt_mcrt_stats.argtypes = [vp, ctypes.POINTER(SkirtStats)]
@@ -172,24 +183,68 @@ def lib():
     return _lib
 
 
+def particle_merge_cap():
+    """The cells of the particle grid that a box may span for a device to compute its mass (partMergeCap of
+    csrc/device/particle_density.hpp); a box spanning more is handed back to the host."""
+    return int(lib().skirt_host_particle_merge_cap())
+
+
 class Simulation:
     """One SKIRT simulation (a .ski file) driven through the native host library."""
 
-    def __init__(self, ski, packages=0.0, seed=0, datadir=None, setup_device=None):
+    def __init__(self, ski, packages=0.0, seed=0, datadir=None, setup_device=None, input_path=None):
         """setup_device: a HIP device for the setup's density sampling (tree subdivision, cell densities);
         None keeps the setup on the host, bit-identical to the reference. A Cylinder2DDustGrid (info.grid_kind ==
         GRID_CYLINDER2D) samples its cell densities on the host either way: the device sampler draws positions in
         boxes, a cylindrical cell draws (R, phi, z). The same holds for a Sphere1DDustGrid and a Sphere2DDustGrid
-        (GRID_SPHERE1D, GRID_SPHERE2D), whose cells draw (direction, r) and (r, theta, phi)."""
+        (GRID_SPHERE1D, GRID_SPHERE2D), whose cells draw (direction, r) and (r, theta, phi).
+        input_path: the folder where a relative file name of the model (the particle file of an
+        SPHDustDistribution) is looked up; None: the .ski file's own folder."""
         L = lib()
-        self._h = L.skirt_sim_load_ex(os.fspath(ski).encode(), (datadir or DATA_DIR).encode(), float(packages),
-                                      int(seed), -1 if setup_device is None else int(setup_device))
+        dev = -1 if setup_device is None else int(setup_device)
+        if input_path is None:
+            self._h = L.skirt_sim_load_ex(os.fspath(ski).encode(), (datadir or DATA_DIR).encode(), float(packages),
+                                          int(seed), dev)
+        else:
+            self._h = L.skirt_sim_load_in(os.fspath(ski).encode(), (datadir or DATA_DIR).encode(), float(packages),
+                                          int(seed), dev, os.fspath(input_path).encode())
         if not self._h:
             raise SkirtError(L.skirt_sim_error().decode())
         info = SkirtSimInfo()
         L.skirt_sim_info(self._h, ctypes.byref(info))
         self.info = info
         self.attached = False
+
+    def particle_info(self):
+        """Imported particle dust: dict(nparticles, nignored, mass_interface, separators (3, 21): the particle grid's
+        x, y and z separators, in metres)."""
+        n, ig, mi = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        sep = np.zeros((3, 21))
+        self._check(lib().skirt_sim_particle_info(self._h, ctypes.byref(n), ctypes.byref(ig), ctypes.byref(mi),
+                                                  sep.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return dict(nparticles=n.value, nignored=ig.value, mass_interface=bool(mi.value), separators=sep)
+
+    def particle_density(self, points, device=None):
+        """SPHDustDistribution::density at points (n, 3), in metres: by the host's functions (device None) or on that
+        HIP device."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(len(pts))
+        dp = ctypes.POINTER(ctypes.c_double)
+        self._check(lib().skirt_sim_particle_density(self._h, -1 if device is None else int(device), len(pts),
+                                                     pts.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+        return out
+
+    def particle_mass_in_box(self, boxes, device=None):
+        """SPHDustDistribution::massInBox of boxes (n, 6: min xyz, max xyz, in metres); returns (masses, the number of
+        boxes a device handed back to the host: 0 with device None)."""
+        bx = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)
+        out = np.zeros(len(bx))
+        back = ctypes.c_size_t()
+        dp = ctypes.POINTER(ctypes.c_double)
+        self._check(lib().skirt_sim_particle_mass_in_box(self._h, -1 if device is None else int(device), len(bx),
+                                                         bx.ctypes.data_as(dp), out.ctypes.data_as(dp),
+                                                         ctypes.byref(back)))
+        return out, back.value
 
     def set_photon_seed(self, seed):
         """Seed of the photon phases' random streams; the grid and other setup draws keep the setup seed."""

@@ -1810,6 +1810,7 @@ __global__ void __launch_bounds__(kBlock) contKernel(const Args a) {
 }
 
 #include "density_sample.hpp"
+#include "particle_kernels.hpp"
 
 // polProbeOne (polarization.hpp) on n packet states, one per thread (skirt_mcrt_scatterings)
 __global__ void __launch_bounds__(kBlock)
@@ -1960,6 +1961,12 @@ void launchScatterings(dim3 grid, hipStream_t st, const double* tab, int ncomp, 
 }
 void launchDensitySample(dim3 grid, hipStream_t st, const DensArgs& d) {
     hipLaunchKernelGGL(densitySampleKernel, grid, dim3(kBlock), 0, st, d);
+}
+void launchParticleSample(dim3 grid, hipStream_t st, const PartArgs& a) {
+    hipLaunchKernelGGL(particleSampleKernel, grid, dim3(kBlock), 0, st, a);
+}
+void launchParticleMass(dim3 grid, hipStream_t st, const PartArgs& a, unsigned* handedBack) {
+    hipLaunchKernelGGL(particleMassKernel, grid, dim3(partMassBlock), 0, st, a, handedBack);
 }
 
 }  // namespace skirt_dev

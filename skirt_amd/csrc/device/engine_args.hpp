@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../../include/skirt_mcrt.h"
+#include "particle_density.hpp"
 
 #define SKIRT_HIDDEN __attribute__((visibility("hidden")))  // not among the library's dynamic symbols
 #if defined(__HIPCC__)
@@ -389,6 +390,16 @@ struct DensArgs {
     const double* norm;   // ncomp
     const double* table;  // ncomp x 2 ntab
     const double* boxes;  // n x 6
+    const uint32_t* words;
+    double* out;
+    size_t n;
+};
+
+// the arguments of particleSampleKernel and particleMassKernel (device/particle_kernels.hpp)
+struct PartArgs {
+    PartView view;
+    int nsample, mode;
+    const double* boxes;  // n x 6 (SKIRT_PART_POINTS: n x 3)
     const uint32_t* words;
     double* out;
     size_t n;

@@ -41,6 +41,9 @@ SKIRT_HIDDEN void launchScatterings(dim3 grid, hipStream_t st, const double* tab
                                     const double* states, const double* deviates, double kox, double koy, double koz,
                                     double kyx, double kyy, double kyz, size_t n, double* out);
 SKIRT_HIDDEN void launchDensitySample(dim3 grid, hipStream_t st, const DensArgs& d);
+// (blocks of kBlock threads; the mass kernel's are of partMassBlock)
+SKIRT_HIDDEN void launchParticleSample(dim3 grid, hipStream_t st, const PartArgs& a);
+SKIRT_HIDDEN void launchParticleMass(dim3 grid, hipStream_t st, const PartArgs& a, unsigned* handedBack);
 
 }  // namespace skirt_dev
 

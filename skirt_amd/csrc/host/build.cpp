@@ -103,6 +103,30 @@ Instrument parseInstrument(const Ctx& c, const XmlElement* e) {
     return ins;
 }
 
+// SPHDustDistribution::setupSelfBefore: the imported particles as the dust system's one component. A relative file
+// name is looked up in the input folder (FilePaths::input), by default the .ski file's own folder.
+void parseParticleDust(const Ctx& c, const XmlElement* dd, Model& m) {
+    const double fdust = attr(c, dd, "dustFraction", "", 0);
+    const double Tmax = attr(c, dd, "maximumTemperature", "temperature", 0);
+    if (fdust <= 0.0) throw std::runtime_error("The dust fraction should be positive");
+    const XmlElement* mixEl = dd->item("dustMix");
+    if (!mixEl) throw std::runtime_error("Dust mix was not set");
+    std::string file = dd->get("filename", "");
+    if (file.empty()) throw std::runtime_error("SPHDustDistribution has no filename");
+    if (file[0] != '/') file = (c.inputdir.empty() ? std::string(".") : c.inputdir) + "/" + file;
+    DustComp comp;
+    comp.mix = parseMix(c, mixEl, m.wl);
+    m.particles = readParticles(file, fdust, Tmax);
+    comp.particles = m.particles;
+    comp.nf = m.particles->mass();  // DustDistribution::mass(): what the grids and the outputs take as the total
+    m.dust.push_back(comp);
+    m.polarization = comp.mix.polarization;
+    if (m.polarization && m.continuousScattering)
+        throw std::runtime_error("continuous scattering is not supported with polarised dust mixes (ElectronDustMix)");
+    if (m.polarization && m.dustEmission)
+        throw std::runtime_error("dust emission is not supported with polarised dust mixes (ElectronDustMix)");
+}
+
 // The dust system's properties and its components (geometry, mix, normalization), with DustSystem::setupSelfBefore's
 // checks on the mixes; the grid and the densities follow in loadSki
 void parseDustSystem(const Ctx& c, const XmlElement* ds, Model& m) {
@@ -126,6 +150,10 @@ void parseDustSystem(const Ctx& c, const XmlElement* ds, Model& m) {
         m.storeAbsorption = m.writeMeanIntensity;
     }
     const XmlElement* dd = need(ds, "dustDistribution");
+    if (dd->name == "SPHDustDistribution") {
+        parseParticleDust(c, dd, m);
+        return;
+    }
     if (dd->name != "CompDustDistribution") throw std::runtime_error("unsupported dust distribution " + dd->name);
     for (const XmlElement* dc : dd->items("components")) {
         DustComp comp;
@@ -172,7 +200,8 @@ void parseDustSystem(const Ctx& c, const XmlElement* ds, Model& m) {
 
 // ============================================================ loadSki
 
-Model loadSki(const std::string& path, UniformSource& rng, const std::string& datadir, DensitySampler* sampler) {
+Model loadSki(const std::string& path, UniformSource& rng, const std::string& datadir, DensitySampler* sampler,
+              const std::string& inputdir) {
     auto doc = parseXmlFile(path);
     if (doc->children.empty()) throw std::runtime_error("empty ski file");
     const XmlElement* sim = doc->children.front().get();
@@ -183,7 +212,11 @@ Model loadSki(const std::string& path, UniformSource& rng, const std::string& da
 
     const XmlElement* unitsEl = sim->item("units");
     m.units_system = unitsEl ? unitsEl->name : "ExtragalacticUnits";
-    Ctx c{Units(m.units_system), datadir, &rng, sampler};
+    Ctx c{Units(m.units_system), datadir, &rng, sampler, inputdir};
+    if (c.inputdir.empty()) {  // the .ski file's own folder (the engine's choice)
+        const size_t slash = path.rfind('/');
+        c.inputdir = slash == std::string::npos ? "." : path.substr(0, slash);
+    }
 
     if (const XmlElement* r = sim->item("random")) m.seed = (unsigned long)attrInt(r, "seed", 4357);
     m.packages = attr(c, sim, "packages", "", 1e6);

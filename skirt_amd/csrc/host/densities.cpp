@@ -44,7 +44,7 @@ void sampleCellDensities(Model& m, UniformSource& rng, MakePosition makePosition
 // The Voronoi grid: rejection sampling draws a data-dependent number of deviates, so the positions are drawn one
 // cell after the other (VoronoiMesh::randomPosition, the cell's neighbour sites gathered once);
 // their densities are then summed, in sample order, on worker threads, a chunk of cells at a time
-void sampleVoronoiDensities(Model& m, UniformSource& rng) {
+void sampleVoronoiDensities(Model& m, UniformSource& rng, DensitySampler* sampler) {
     const VoronoiGrid& g = m.grid.vor;
     const int Ncells = m.grid.ncells;
     const int ns = m.sampleCount;
@@ -96,6 +96,17 @@ void sampleVoronoiDensities(Model& m, UniformSource& rng) {
             }
         }
         pst.reset(new StageTimer("voronoi densities"));
+        if (sampler && m.particles) {
+            // particle dust on a device: the density at every position there, summed here in sample order
+            std::vector<double> rhov((size_t)(c1 - c0) * ns);
+            sampler->pointDensity(*m.particles, pos.data(), rhov.size(), rhov.data());
+            for (int cell = c0; cell < c1; cell++) {
+                double sum = 0.0;
+                for (int n = 0; n < ns; n++) sum += rhov[(size_t)(cell - c0) * ns + n];
+                storeCellMeans(m, cell, &sum);
+            }
+            continue;
+        }
         parallelFor((size_t)(c1 - c0), 256, [&](size_t q0, size_t q1) {
             for (size_t q = q0; q < q1; q++)
                 accumulateCell(m, c0 + q, [&](int n, double p[3]) {
@@ -118,7 +129,7 @@ void sampleDensities(const Ctx& c, Model& m) {
     // the cylinder's and the spheres' positions are always the host's (the device sampler draws in boxes)
     const DustGrid& g = m.grid;
     switch (g.kind) {
-    case GridKind::Voronoi: sampleVoronoiDensities(m, rng); return;
+    case GridKind::Voronoi: sampleVoronoiDensities(m, rng, c.sampler); return;
     case GridKind::Cylinder2D:
         sampleCellDensities(m, rng, [&](int cell) { return g.cyl.positionInCell(cell); });
         return;
@@ -130,6 +141,18 @@ void sampleDensities(const Ctx& c, Model& m) {
         return;
     case GridKind::Cartesian:
     case GridKind::Octree: break;
+    }
+    // DustGridDensityInterface (TreeDustGrid::density, offered where the distribution has massInBox): the mass in
+    // the cell's box over its volume, no draws; also for a barycentric tree
+    if (g.kind == GridKind::Octree && m.particles && m.particles->massInterface()) {
+        std::vector<double> boxes(6 * (size_t)Ncells), mass(Ncells);
+        for (int cell = 0; cell < Ncells; cell++) g.cellBox(cell, &boxes[6 * (size_t)cell]);
+        particleMasses(c, *m.particles, boxes.data(), (size_t)Ncells, mass.data());
+        for (int cell = 0; cell < Ncells; cell++) {
+            const double* b = &boxes[6 * (size_t)cell];
+            m.rho[cell] = mass[cell] / ((b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]));  // Box::volume
+        }
+        return;
     }
     // Random::position(box) per sample: three deviates, drawn ahead in cell order; on the device where there is one
     const bool onDevice = deviceSampling(

@@ -261,13 +261,30 @@ void buildVoronoiGrid(const Ctx& c, const XmlElement* ge, Model& m, UniformSourc
     const double ymin = attr(c, ge, "minY", "length", 0), ymax = attr(c, ge, "maxY", "length", 0);
     const double zmin = attr(c, ge, "minZ", "length", 0), zmax = attr(c, ge, "maxZ", "length", 0);
     const int N = attrInt(ge, "numParticles", 0);
-    if (N < 10) throw std::runtime_error("The number of particles should be at least 10");
     const std::string dist = ge->get("distribution", "DustDensity");
+    if (dist != "SPHParticles" && N < 10) throw std::runtime_error("The number of particles should be at least 10");
     auto contains = [&](double x, double y, double z) {  // Box::contains
         return x >= xmin && x <= xmax && y >= ymin && y <= ymax && z >= zmin && z <= zmax;
     };
-    std::vector<double> sites(3 * (size_t)N);
-    if (dist == "Uniform") {
+    std::vector<double> sites(dist == "SPHParticles" ? 0 : 3 * (size_t)N);
+    if (dist == "SPHParticles") {
+        // VoronoiMesh(DustParticleInterface*, extent): the particle centres inside the extent, in file order
+        if (!m.particles) throw std::runtime_error("Can't retrieve particle locations from this dust distribution");
+        for (const PartRec& r : m.particles->rec)
+            if (contains(r.x, r.y, r.z)) sites.insert(sites.end(), {r.x, r.y, r.z});
+    } else if (dist == "DustDensity" && m.particles) {
+        // SPHDustDistribution::generatePosition; points outside the domain are redrawn
+        for (int q = 0; q < N; q++) {
+            while (true) {
+                double x, y, z;
+                m.particles->generatePosition(rng, [](UniformSource& r) { return gaussDeviate(r); }, x, y, z);
+                if (contains(x, y, z)) {
+                    sites[3 * q] = x; sites[3 * q + 1] = y; sites[3 * q + 2] = z;
+                    break;
+                }
+            }
+        }
+    } else if (dist == "Uniform") {
         for (int q = 0; q < N; q++) {
             double fx = rng.uniform(), fy = rng.uniform(), fz = rng.uniform();  // Random::position(extent)
             sites[3 * q] = xmin + fx * (xmax - xmin);
@@ -297,6 +314,9 @@ void buildVoronoiGrid(const Ctx& c, const XmlElement* ge, Model& m, UniformSourc
                 }
             }
         }
+    } else if (dist == "DustTesselation" || dist == "File") {
+        throw std::runtime_error("the Voronoi particle distribution " + dist +
+                                 " is not supported (imported Voronoi meshes are out of scope)");
     } else {
         throw std::runtime_error("unsupported Voronoi particle distribution " + dist);
     }
@@ -369,6 +389,11 @@ void parseSphereGrid(const Ctx& c, const XmlElement* ge, Model& m) {
 void checkGridDimension(const XmlElement* ge, const Model& m) {
     const int dimGrid = ge->name == "Sphere1DDustGrid" ? 1
                         : (ge->name == "Sphere2DDustGrid" || ge->name == "Cylinder2DDustGrid") ? 2 : 3;
+    // particle dust: SPHDustDistribution::dimension() is 3, and DustGrid::setupSelfBefore compares the grid with the
+    // dust distribution
+    if (m.particles && dimGrid < 3)
+        throw std::runtime_error("The grid dimension " + std::to_string(dimGrid) +
+                                 " is lower than the geometry dimension 3");
     int dimGeometry = 0;
     for (const Geometry& sg : m.starGeom)
         if (isAnisotropic(sg.kind)) dimGeometry = std::max(dimGeometry, anisoDimension(sg.kind));
@@ -403,6 +428,8 @@ void parseDustGrid(const Ctx& c, const XmlElement* ge, Model& m) {
     else if (ge->name == "VoronoiDustGrid") parseVoronoiGrid(c, ge, m);
     else if (ge->name == "Cylinder2DDustGrid") parseCylinder2DGrid(c, ge, m);
     else if (ge->name == "Sphere1DDustGrid" || ge->name == "Sphere2DDustGrid") parseSphereGrid(c, ge, m);
+    else if (ge->name == "ParticleTreeDustGrid")
+        throw std::runtime_error("ParticleTreeDustGrid is not supported (use an OctTreeDustGrid or a BinTreeDustGrid)");
     else throw std::runtime_error("unsupported dust grid " + ge->name);
 }
 

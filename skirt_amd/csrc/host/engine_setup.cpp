@@ -829,4 +829,130 @@ int skirt_mcrt_sample_density(int device, const SkirtDensityDesc* dens, const do
     return rc;
 }
 
+// ------------------------------------------------------------------ imported particle dust
+struct SkirtParticles {
+    int device = 0;
+    hipStream_t st = nullptr;
+    char* buf = nullptr;  // one allocation: records, separators, erf table, offsets, lists
+    unsigned* dBack = nullptr;
+    PartView view{};
+};
+
+void skirt_mcrt_particles_free(SkirtParticles* p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    if (p->st) (void)hipStreamSynchronize(p->st);
+    if (p->buf) (void)hipFree(p->buf);
+    if (p->dBack) (void)hipFree(p->dBack);
+    if (p->st) (void)hipStreamDestroy(p->st);
+    delete p;
+}
+
+int skirt_mcrt_particles_upload(int device, const SkirtParticlesDesc* d, SkirtParticles** out) {
+    if (!out) return SKIRT_ERR_ARG;
+    *out = nullptr;
+    constexpr int ncell = partGrid * partGrid * partGrid, nsep = 3 * (partGrid + 1);
+    if (!d || d->nparticles < 1 || !d->rec || !d->separators || !d->cell_offset || !d->cell_list || !d->erf_table)
+        return SKIRT_ERR_ARG;
+    // every offset and index the kernels will follow, checked here: offsets ascending from 0, ids inside the particle
+    // array and ascending within a cell (the ordered merge relies on it)
+    if (d->cell_offset[0] != 0) return SKIRT_ERR_ARG;
+    for (int c = 0; c < ncell; c++) {
+        if (d->cell_offset[c + 1] < d->cell_offset[c]) return SKIRT_ERR_ARG;
+        for (int q = d->cell_offset[c]; q < d->cell_offset[c + 1]; q++) {
+            const int id = d->cell_list[q];
+            if (id < 0 || id >= d->nparticles || (q > d->cell_offset[c] && id <= d->cell_list[q - 1])) return SKIRT_ERR_ARG;
+        }
+    }
+    const size_t nlist = (size_t)d->cell_offset[ncell];
+    const size_t offRec = 0, offSep = offRec + (size_t)d->nparticles * sizeof(PartRec);
+    const size_t offErf = offSep + nsep * sizeof(double);
+    const size_t offOff = offErf + (partErfN + 1) * sizeof(double);
+    const size_t offList = offOff + (ncell + 1) * sizeof(int);
+    const size_t total = offList + (nlist ? nlist : 1) * sizeof(int);
+    auto* p = new SkirtParticles();
+    p->device = device;
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking) != hipSuccess ||
+        hipMalloc(&p->buf, total) != hipSuccess || hipMalloc(&p->dBack, sizeof(unsigned)) != hipSuccess ||
+        hipMemcpyAsync(p->buf + offRec, d->rec, (size_t)d->nparticles * sizeof(PartRec), hipMemcpyHostToDevice, p->st) != hipSuccess ||
+        hipMemcpyAsync(p->buf + offSep, d->separators, nsep * sizeof(double), hipMemcpyHostToDevice, p->st) != hipSuccess ||
+        hipMemcpyAsync(p->buf + offErf, d->erf_table, (partErfN + 1) * sizeof(double), hipMemcpyHostToDevice, p->st) != hipSuccess ||
+        hipMemcpyAsync(p->buf + offOff, d->cell_offset, (ncell + 1) * sizeof(int), hipMemcpyHostToDevice, p->st) != hipSuccess ||
+        (nlist && hipMemcpyAsync(p->buf + offList, d->cell_list, nlist * sizeof(int), hipMemcpyHostToDevice, p->st) != hipSuccess) ||
+        hipStreamSynchronize(p->st) != hipSuccess) {
+        skirt_mcrt_particles_free(p);
+        return SKIRT_ERR_HIP;
+    }
+    p->view.rec = reinterpret_cast<const PartRec*>(p->buf + offRec);
+    p->view.sep = reinterpret_cast<const double*>(p->buf + offSep);
+    p->view.erfTable = reinterpret_cast<const double*>(p->buf + offErf);
+    p->view.cellOffset = reinterpret_cast<const int*>(p->buf + offOff);
+    p->view.cellList = reinterpret_cast<const int*>(p->buf + offList);
+    p->view.fdust = d->dust_fraction;
+    p->view.nparticles = d->nparticles;
+    *out = p;
+    return SKIRT_OK;
+}
+
+namespace {
+// one call of either particle kernel: items in (nin doubles each), words (sampling only), out (nout doubles each)
+int runParticles(SkirtParticles* p, const double* in, size_t nin, size_t n, const uint32_t* words, int nsample, int mode,
+                 size_t nout, bool massKernel, double* out, size_t* handedBack) {
+    const size_t nw = words ? n * 3 * (size_t)nsample : 0;
+    const int block = massKernel ? partMassBlock : kBlock;
+    const size_t nblocks = (n + block - 1) / block;
+    if (nblocks > 0x7fffffffu) return SKIRT_ERR_ARG;
+    if (hipSetDevice(p->device) != hipSuccess) return SKIRT_ERR_HIP;
+    const size_t offOut = (nin * n * sizeof(double) + 15) & ~(size_t)15;
+    const size_t offWords = (offOut + nout * n * sizeof(double) + 15) & ~(size_t)15;
+    char* buf = nullptr;
+    if (hipMalloc(&buf, offWords + (nw ? nw : 1) * sizeof(uint32_t)) != hipSuccess) return SKIRT_ERR_HIP;
+    PartArgs a{};
+    a.view = p->view;
+    a.nsample = nsample;
+    a.mode = mode;
+    a.boxes = reinterpret_cast<const double*>(buf);
+    a.out = reinterpret_cast<double*>(buf + offOut);
+    a.words = reinterpret_cast<const uint32_t*>(buf + offWords);
+    a.n = n;
+    int rc = SKIRT_OK;
+    unsigned back = 0;
+    if (hipMemcpyAsync(buf, in, nin * n * sizeof(double), hipMemcpyHostToDevice, p->st) != hipSuccess ||
+        (nw && hipMemcpyAsync(buf + offWords, words, nw * sizeof(uint32_t), hipMemcpyHostToDevice, p->st) != hipSuccess) ||
+        (massKernel && hipMemsetAsync(p->dBack, 0, sizeof(unsigned), p->st) != hipSuccess)) {
+        rc = SKIRT_ERR_HIP;
+    } else {
+        if (massKernel) launchParticleMass(dim3((unsigned)nblocks), p->st, a, p->dBack);
+        else launchParticleSample(dim3((unsigned)nblocks), p->st, a);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(out, buf + offOut, nout * n * sizeof(double), hipMemcpyDeviceToHost, p->st) != hipSuccess ||
+            (massKernel && hipMemcpyAsync(&back, p->dBack, sizeof(unsigned), hipMemcpyDeviceToHost, p->st) != hipSuccess) ||
+            hipStreamSynchronize(p->st) != hipSuccess)
+            rc = SKIRT_ERR_HIP;
+    }
+    (void)hipStreamSynchronize(p->st);
+    (void)hipFree(buf);
+    if (handedBack) *handedBack = back;
+    return rc;
+}
+}  // namespace
+
+int skirt_mcrt_particles_sample(SkirtParticles* p, const double* boxes, size_t n, const uint32_t* words, int nsample,
+                                int mode, double* out) {
+    const bool points = mode == SKIRT_PART_POINTS;
+    if (!p || (mode != SKIRT_DENS_COMPONENTS && mode != SKIRT_DENS_NODE && !points) || (!points && nsample < 1) ||
+        (n && (!boxes || !out || (!points && !words))))
+        return SKIRT_ERR_ARG;
+    if (n == 0) return SKIRT_OK;
+    return runParticles(p, boxes, points ? 3 : 6, n, points ? nullptr : words, points ? 0 : nsample, mode,
+                        mode == SKIRT_DENS_NODE ? 6 : 1, false, out, nullptr);
+}
+
+int skirt_mcrt_particles_mass_in_box(SkirtParticles* p, const double* boxes, size_t n, double* out, size_t* handed_back) {
+    if (handed_back) *handed_back = 0;
+    if (!p || (n && (!boxes || !out))) return SKIRT_ERR_ARG;
+    if (n == 0) return SKIRT_OK;
+    return runParticles(p, boxes, 6, n, nullptr, 0, 0, 1, true, out, handed_back);
+}
+
 }  // extern "C"

@@ -1,6 +1,8 @@
 // skirt-mi355x: runs the stellar emission phase of a .ski file on one MI355X and writes SKIRT-format
 // outputs (the counterpart of `skirt <file.ski>` for the photon-shooting path, SKIRTmain/SkirtMain.cpp).
-//   skirt-mi355x [-d device | -g ngpus] [-o outprefix] [-p packages] [-s seed] file.ski
+//   skirt-mi355x [-d device | -g ngpus] [-i inputdir] [-o outprefix] [-p packages] [-s seed] file.ski
+// -i DIR is where a relative file name of the model (an imported particle file) is looked up, as the reference's -i;
+// without it, the .ski file's own folder.
 // -g N runs the simulation on devices 0 .. N-1 of this node: each shoots its slice of every wavelength and
 // the tallies are summed over xGMI by RCCL all-reduces at each phase end (skirt_sim_run_devices).
 #include <chrono>
@@ -15,22 +17,27 @@ int main(int argc, char** argv) {
     int device = 0, ngpus = 0;
     double packages = 0;
     unsigned long long seed = 0;
-    std::string out, ski;
+    std::string out, ski, in;
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "-d") && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-g") && i + 1 < argc) ngpus = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
+        else if (!std::strcmp(argv[i], "-i") && i + 1 < argc) in = argv[++i];
         else if (!std::strcmp(argv[i], "-p") && i + 1 < argc) packages = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "-s") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
         else ski = argv[i];
     }
     if (ski.empty()) {
-        std::fprintf(stderr, "usage: skirt-mi355x [-d device | -g ngpus] [-o outprefix] [-p packages] [-s seed] file.ski\n");
+        std::fprintf(stderr, "usage: skirt-mi355x [-d device | -g ngpus] [-i inputdir] [-o outprefix] [-p packages] [-s seed] file.ski\n");
         return 2;
     }
     if (out.empty()) {
         out = ski;
         if (out.size() > 4 && out.substr(out.size() - 4) == ".ski") out.resize(out.size() - 4);
+    }
+    if (ngpus > 0 && !in.empty()) {  // (skirt_sim_run_devices loads the model itself and takes no input folder)
+        std::fprintf(stderr, "*** Error: -i is not supported with -g; put the input files beside the .ski file\n");
+        return 2;
     }
     if (ngpus > 0) {
         SkirtStats st;
@@ -43,7 +50,7 @@ int main(int argc, char** argv) {
                     ngpus, (unsigned long long)st.packets, secs);
         return 0;
     }
-    SkirtSim* sim = skirt_sim_load(ski.c_str(), nullptr, packages, seed);
+    SkirtSim* sim = skirt_sim_load_in(ski.c_str(), nullptr, packages, seed, -1, in.c_str());
     if (!sim) { std::fprintf(stderr, "*** Error: %s\n", skirt_sim_error()); return 1; }
     SkirtSimInfo info;
     skirt_sim_info(sim, &info);

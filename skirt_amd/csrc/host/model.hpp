@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "mt_random.hpp"
+#include "particles.hpp"
 #include "units.hpp"
 #include "voronoi.hpp"
 #include "../device/aniso_emission.hpp"
@@ -277,8 +278,13 @@ struct DustMix {
 struct DustComp {
     Geometry geom;
     DustMix mix;
-    double nf = 0;  // normalization factor = dust mass (DustMassDustCompNormalization)
-    double density(double x, double y, double z) const { return nf * geom.density(x, y, z); }
+    double nf = 0;  // normalization factor = dust mass (DustMassDustCompNormalization); particle dust: mass()
+    // imported particle dust (SPHDustDistribution, particles.hpp): the one component's density is the particle
+    // set's, geom is not looked at
+    std::shared_ptr<const ParticleSet> particles;
+    double density(double x, double y, double z) const {
+        return particles ? particles->density(x, y, z) : nf * geom.density(x, y, z);
+    }
 };
 
 // The grids of every kind, each with its cells' geometry read together (dustgrid.cpp): the box or the volume and
@@ -484,6 +490,8 @@ struct Model {
     bool hasDust = false;
     bool polarization = false;  // DustSystem::polarization(): every dust mix supports polarisation
     std::vector<DustComp> dust;
+    // SPHDustDistribution: the particle set (dust then holds its one component, which shares it); null otherwise
+    std::shared_ptr<const ParticleSet> particles;
     DustGrid grid;
     std::vector<double> rho;     // Ncells x Ncomp row-major (DustSystem::_rhovv)
     std::vector<double> volume;  // per cell
@@ -511,8 +519,13 @@ struct Model {
 enum DensityMode : int { kDensComponents = 0, kDensNode = 1 };  // SKIRT_DENS_COMPONENTS, SKIRT_DENS_NODE
 struct DensitySampler {
     virtual ~DensitySampler() = default;
+    // (a particle component, dust[0].particles, samples the particle density: one component)
     virtual void sample(const std::vector<DustComp>& dust, const double* boxes, size_t n, const uint32_t* words,
                         int nsample, int mode, double* out) = 0;
+    // particle dust: the mass in each of n boxes (SPHDustDistribution::massInBox), and the density at each of n
+    // points; handedBack (may be null) receives the number of boxes the device left to the host's worker threads
+    virtual void massInBox(const ParticleSet& ps, const double* boxes, size_t n, double* out, size_t* handedBack) = 0;
+    virtual void pointDensity(const ParticleSet& ps, const double* points, size_t n, double* out) = 0;
     // the Voronoi tessellation's cells on the same device (null: on the host)
     virtual const VoronoiCellsFn* voronoiCells() const { return nullptr; }
 };
@@ -521,8 +534,10 @@ struct DensitySampler {
 // sampling, cell density sampling) in the reference's order. `datadir` holds SunSED.bin etc. With a
 // sampler (and a Mersenne-twister rng), the density sampling of the tree subdivision and of the cell
 // densities runs on its device; the host still draws every random number and takes every decision.
+// `inputdir` is where a relative file name of the model (an imported particle file) is looked up; empty: the .ski
+// file's own folder.
 Model loadSki(const std::string& path, UniformSource& rng, const std::string& datadir,
-              DensitySampler* sampler = nullptr);
+              DensitySampler* sampler = nullptr, const std::string& inputdir = std::string());
 
 // directory holding the packaged resource tables (skirt_amd/data), located relative to this library
 std::string defaultDataDir();

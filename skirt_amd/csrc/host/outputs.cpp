@@ -370,6 +370,7 @@ void writeConvergence(const Model& m, const std::string& prefix, const double si
     int dim = 1;
     double ref[3] = {0, 0, 0}, Mref = 0;
     for (auto& d : m.dust) {
+        if (d.particles) break;
         const GeometryKind gk = d.geom.kind;  // AxGeometry (dimension 2) or SpheGeometry (dimension 1)
         const bool ax = gk == GeometryKind::ExpDisk || gk == GeometryKind::Gaussian || gk == GeometryKind::TTauriDisk ||
                         gk == GeometryKind::Torus || gk == GeometryKind::ConicalShell;
@@ -389,7 +390,13 @@ void writeConvergence(const Model& m, const std::string& prefix, const double si
         f.line("         expected value = " + num(expected));
         f.line("         actual value =   " + num(actual));
     };
-    if (dim == 1) {
+    if (m.particles) {
+        // SPHDustDistribution: dimension 3, SigmaX / SigmaY / SigmaZ along the particle grid's axes, mass()
+        pair("X-axis surface density", m.particles->Sigma(0), sigma[0]);
+        pair("Y-axis surface density", m.particles->Sigma(1), sigma[1]);
+        pair("Z-axis surface density", m.particles->Sigma(2), sigma[2]);
+        Mref = m.particles->mass();
+    } else if (dim == 1) {
         pair("radial (r-axis) surface density", 0.5 * ref[0], 0.5 * sigma[0]);
     } else {
         pair("edge-on (R-axis) surface density", 0.5 * ref[0], 0.5 * sigma[0]);

@@ -30,7 +30,7 @@ void writeCellsCrossed(const Model& m, const std::string& prefix, const std::vec
 // DustSystem::writeconvergence (DustSystem.cpp:195-305): <prefix>_ds_convergence.dat, the grid's mass and
 // column densities through the origin (sigma: x, y and z axes, each the sum of its two half axes) beside
 // the dust distribution's analytic values. The geometries here are spherical (dimension 1) or axisymmetric
-// (ExpDisk, dimension 2); the dimension-3 branch of the reference has no geometry to reach it.
+// (ExpDisk, dimension 2); imported particle dust takes the reference's dimension-3 branch.
 void writeConvergence(const Model& m, const std::string& prefix, const double sigma[3]);
 
 // Qt-compatible number formatting: QString::number(v, 'e', prec) and QString::number(v, 'g', prec)

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -14,6 +15,7 @@
 #include "dustemission.hpp"
 #include "model.hpp"
 #include "outputs.hpp"
+#include "workers.hpp"
 #include "../device/philox.hpp"
 #include "../device/polarization.hpp"
 
@@ -39,6 +41,8 @@ struct SkirtSim {
     std::vector<double> instrAll;             // concatenated, per instrument frames [slot][lambda][pixel] + SEDs
     std::vector<size_t> instrOff;             // per instrument offset into instrAll
     std::vector<std::vector<double>> frames, seds;
+    // per HIP device, the sampler that holds this simulation's uploaded particle set (the set-up's, and the probes')
+    std::map<int, std::shared_ptr<DensitySampler>> samplers;
     ~SkirtSim() {
         if (eng) skirt_mcrt_destroy(eng);
     }
@@ -160,10 +164,62 @@ VoronoiCellsFn deviceVoronoiCells(int device) {
 struct DeviceDensitySampler final : DensitySampler {
     int device;
     VoronoiCellsFn cells;
+    // an imported particle set on the device: uploaded once, when first used
+    const ParticleSet* uploaded = nullptr;
+    SkirtParticles* parts = nullptr;
     explicit DeviceDensitySampler(int d) : device(d), cells(deviceVoronoiCells(d)) {}
+    ~DeviceDensitySampler() override { skirt_mcrt_particles_free(parts); }
     const VoronoiCellsFn* voronoiCells() const override { return &cells; }
+    [[noreturn]] void fail(const char* what, int rc) const {
+        throw std::runtime_error(std::string(what) + " on device " + std::to_string(device) + " failed (error " +
+                                 std::to_string(rc) + ")");
+    }
+    SkirtParticles* handle(const ParticleSet& ps) {
+        if (uploaded == &ps) return parts;
+        skirt_mcrt_particles_free(parts);
+        parts = nullptr;
+        uploaded = nullptr;
+        static_assert(sizeof(PartRec) == 8 * sizeof(double), "a particle record is eight doubles");
+        const SkirtParticlesDesc d{ps.size(), reinterpret_cast<const double*>(ps.rec.data()), ps.sep, ps.cellOffset.data(),
+                                   ps.cellList.data(), ps.erfTable.data(), ps.fdust};
+        const int rc = skirt_mcrt_particles_upload(device, &d, &parts);
+        if (rc) fail("the particle upload", rc);
+        uploaded = &ps;
+        return parts;
+    }
+    void massInBox(const ParticleSet& ps, const double* boxes, size_t n, double* out, size_t* handedBack) override {
+        // the boxes beyond the kernel's merge cap go to worker threads, which run beside the kernel
+        std::vector<size_t> over;
+        for (size_t q = 0; q < n; q++)
+            if (ps.boxCells(boxes + 6 * q) > partMergeCap) over.push_back(q);
+        std::vector<double> hostOut(over.size());
+        SkirtParticles* h = handle(ps);
+        size_t back = 0;
+        int rc = SKIRT_OK;
+        parallelFor(
+            over.size(), 4,
+            [&](size_t i0, size_t i1) {
+                for (size_t i = i0; i < i1; i++) hostOut[i] = ps.massInBox(boxes + 6 * over[i]);
+            },
+            [&] { rc = skirt_mcrt_particles_mass_in_box(h, boxes, n, out, &back); });
+        if (rc) fail("the particle mass in boxes", rc);
+        if (back != over.size())
+            throw std::runtime_error("the device handed back " + std::to_string(back) + " boxes, the host counted " +
+                                     std::to_string(over.size()) + " beyond the merge cap");
+        for (size_t i = 0; i < over.size(); i++) out[over[i]] = hostOut[i];
+        if (handedBack) *handedBack = back;
+    }
+    void pointDensity(const ParticleSet& ps, const double* points, size_t n, double* out) override {
+        const int rc = skirt_mcrt_particles_sample(handle(ps), points, n, nullptr, 0, SKIRT_PART_POINTS, out);
+        if (rc) fail("the particle density", rc);
+    }
     void sample(const std::vector<DustComp>& dust, const double* boxes, size_t n, const uint32_t* words, int nsample,
                 int mode, double* out) override {
+        if (dust.size() == 1 && dust[0].particles) {
+            const int rc = skirt_mcrt_particles_sample(handle(*dust[0].particles), boxes, n, words, nsample, mode, out);
+            if (rc) fail("particle density sampling", rc);
+            return;
+        }
         const int nc = (int)dust.size();
         std::vector<int> kind(nc);
         std::vector<double> param(8 * (size_t)nc), norm(nc), table;
@@ -198,6 +254,11 @@ SkirtSim* skirt_sim_load(const char* ski, const char* datadir, double packages, 
 }
 
 SkirtSim* skirt_sim_load_ex(const char* ski, const char* datadir, double packages, uint64_t seed, int setup_device) {
+    return skirt_sim_load_in(ski, datadir, packages, seed, setup_device, nullptr);
+}
+
+SkirtSim* skirt_sim_load_in(const char* ski, const char* datadir, double packages, uint64_t seed, int setup_device,
+                            const char* input_path) {
     try {
         auto s = std::make_unique<SkirtSim>();
         auto t0 = std::chrono::steady_clock::now();
@@ -206,9 +267,11 @@ SkirtSim* skirt_sim_load_ex(const char* ski, const char* datadir, double package
         // deviates reject forever (the reference hangs in its setup); refuse it
         if ((theSeed & 0xffffffffUL) == 0) throw std::runtime_error("random seed 0 (mod 2^32) is not usable");
         MTRandom mt(theSeed);  // setup draws exactly like the reference (density / tree sampling)
-        std::unique_ptr<DeviceDensitySampler> sampler;
+        std::shared_ptr<DeviceDensitySampler> sampler;
         if (setup_device >= 0) sampler.reset(new DeviceDensitySampler(setup_device));
-        s->m = loadSki(ski, mt, datadir && *datadir ? datadir : defaultDataDir(), sampler.get());
+        s->m = loadSki(ski, mt, datadir && *datadir ? datadir : defaultDataDir(), sampler.get(),
+                       input_path ? input_path : "");
+        if (sampler && s->m.particles) s->samplers[setup_device] = sampler;  // keeps the uploaded particle set
         s->m.seed = theSeed;
         if (packages > 0) s->m.packages = packages;
         s->npp = (uint64_t)std::ceil(s->m.packages);
@@ -243,6 +306,66 @@ int skirt_sim_info(SkirtSim* s, SkirtSimInfo* o) {
     o->has_dust = s->m.hasDust;
     o->setup_seconds = s->setupSeconds;
     return SKIRT_OK;
+}
+
+int skirt_host_particle_merge_cap(void) { return partMergeCap; }
+
+int skirt_sim_particle_info(SkirtSim* s, int* nparticles, int* nignored, int* mass_interface, double* separators) {
+    if (!s || !s->m.particles) {
+        g_err = "the model has no particle dust (SPHDustDistribution)";
+        return SKIRT_ERR_ARG;
+    }
+    const ParticleSet& ps = *s->m.particles;
+    if (nparticles) *nparticles = ps.size();
+    if (nignored) *nignored = ps.nignored;
+    if (mass_interface) *mass_interface = ps.massInterface();
+    if (separators) std::copy(ps.sep, ps.sep + 3 * (partGrid + 1), separators);
+    return SKIRT_OK;
+}
+
+namespace {
+// the sampler of `device` that holds this simulation's particle set
+DensitySampler& particleSampler(SkirtSim* s, int device) {
+    auto& sp = s->samplers[device];
+    if (!sp) sp.reset(new DeviceDensitySampler(device));
+    return *sp;
+}
+}  // namespace
+
+int skirt_sim_particle_density(SkirtSim* s, int device, size_t n, const double* points, double* out) {
+    if (!s || !s->m.particles || (n && (!points || !out))) {
+        g_err = "no particle dust, or a null buffer";
+        return SKIRT_ERR_ARG;
+    }
+    try {
+        const ParticleSet& ps = *s->m.particles;
+        if (n == 0) return SKIRT_OK;
+        if (device >= 0) particleSampler(s, device).pointDensity(ps, points, n, out);
+        else for (size_t i = 0; i < n; i++) out[i] = ps.density(points[3 * i], points[3 * i + 1], points[3 * i + 2]);
+        return SKIRT_OK;
+    } catch (std::exception& e) {
+        g_err = e.what();
+        return SKIRT_ERR_HIP;
+    }
+}
+
+int skirt_sim_particle_mass_in_box(SkirtSim* s, int device, size_t n, const double* boxes, double* out,
+                                   size_t* handed_back) {
+    if (handed_back) *handed_back = 0;
+    if (!s || !s->m.particles || (n && (!boxes || !out))) {
+        g_err = "no particle dust, or a null buffer";
+        return SKIRT_ERR_ARG;
+    }
+    try {
+        const ParticleSet& ps = *s->m.particles;
+        if (n == 0) return SKIRT_OK;
+        if (device >= 0) particleSampler(s, device).massInBox(ps, boxes, n, out, handed_back);
+        else for (size_t i = 0; i < n; i++) out[i] = ps.massInBox(boxes + 6 * i);
+        return SKIRT_OK;
+    } catch (std::exception& e) {
+        g_err = e.what();
+        return SKIRT_ERR_HIP;
+    }
 }
 
 int skirt_sim_set_photon_seed(SkirtSim* s, uint64_t seed) {

@@ -36,6 +36,7 @@ struct Ctx {
     std::string datadir;
     UniformSource* rng;
     DensitySampler* sampler = nullptr;  // device density sampling (null: host threads)
+    std::string inputdir;               // where relative input file names are looked up
 };
 
 // ------------------------------------------------------------ .ski attributes
@@ -86,6 +87,8 @@ double mixKappaext(const DustMix& mix, const WavelengthGrid& wl, double lambda);
 // through treegrid.cpp, which samples the dust density on c.rng as it subdivides
 void parseDustGrid(const Ctx& c, const XmlElement* ge, Model& m);
 void buildOctree(const Ctx& c, const XmlElement* e, const Model& model, OctreeGrid& t, bool binary);
+// treegrid.cpp: particle dust's massInBox of n boxes, on the sampler's device or on worker threads
+void particleMasses(const Ctx& c, const ParticleSet& ps, const double* boxes, size_t n, double* out);
 // densities.cpp: DustSystem::setupSelfAfter, the cell volumes and the sampled densities (m.volume, m.rho)
 void sampleDensities(const Ctx& c, Model& m);
 

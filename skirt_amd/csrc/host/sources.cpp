@@ -135,6 +135,9 @@ void parseStellarSystem(const Ctx& c, const XmlElement* ss, Model& m) {
     const int Nlambda = m.wl.n();
     m.starEmissionBias = attr(c, ss, "emissionBias", "", 0.5);
     for (const XmlElement* sc : ss->items("components")) {
+        if (sc->name == "SPHStellarComp")  // imported star particles take an SED family
+            throw std::runtime_error("SPHStellarComp is not supported: its SED family tables (Bruzual-Charlot) are "
+                                     "not packaged");
         m.starGeom.push_back(parseGeometry(c, need(sc, "geometry")));
         if (sc->name == "OligoStellarComp") {
             if (m.pan) throw std::runtime_error("OligoStellarComp requires an oligochromatic simulation");

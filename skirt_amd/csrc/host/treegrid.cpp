@@ -11,6 +11,18 @@
 
 namespace skirt {
 
+// SPHDustDistribution::massInBox of n boxes: on the sampler's device where there is one, else on worker threads
+void particleMasses(const Ctx& c, const ParticleSet& ps, const double* boxes, size_t n, double* out) {
+    if (n == 0) return;
+    if (c.sampler) {
+        c.sampler->massInBox(ps, boxes, n, out, nullptr);
+        return;
+    }
+    parallelFor(n, 16, [&](size_t q0, size_t q1) {
+        for (size_t q = q0; q < q1; q++) out[q] = ps.massInBox(boxes + 6 * q);
+    });
+}
+
 // TreeDustGrid::setupSelfBefore / subdivide (TreeDustGrid.cpp:50-233), OctTreeNode (OctTreeNode.cpp),
 // TreeNode neighbor bookkeeping (TreeNode.cpp). Nodes are kept as indices into flat arrays; the
 // neighbor lists are std::vector<int> per (node, wall) mutated in exactly the reference's order so that
@@ -219,7 +231,10 @@ void buildOctree(const Ctx& c, const XmlElement* e, const Model& model, OctreeGr
     double wx = t.xmax - t.xmin, wy = t.ymax - t.ymin, wz = t.zmax - t.zmin;
     t.eps = 1e-12 * std::sqrt(wx * wx + wy * wy + wz * wz);
     double totalmass = 0;
-    for (auto& d : model.dust) totalmass += d.nf;  // CompDustDistribution::mass
+    for (auto& d : model.dust) totalmass += d.nf;  // CompDustDistribution::mass (particle dust: nf is its mass())
+    // TreeDustGrid::setupSelfBefore: _useDmibForSubdivide, which a barycentric tree turns off (OctTreeDustGrid.cpp:36,
+    // BinTreeDustGrid.cpp:48)
+    const bool massSubdivide = model.particles && model.particles->massInterface() && maxDensDispFraction == 0 && !bary;
 
     TreeBuilder tb(t);
     tb.addNode(-1, t.xmin, t.ymin, t.zmin, t.xmax, t.ymax, t.zmax);
@@ -238,11 +253,8 @@ void buildOctree(const Ctx& c, const XmlElement* e, const Model& model, OctreeGr
         std::vector<std::array<double, 3>> bc(bary ? l1 - l0 : 0);  // sampled barycentres
         for (size_t l = l0; l < l1; l++) divide[l - l0] = t.level[l] <= t.minLevel;
         // the subdivision criteria of a sampled node from its mass, barycentre and density range
-        auto decide = [&](int l, double sumrho, double sx, double sy, double sz, double mn, double mx) {
-            const double* b = tb.box(l);
-            if (bary) bc[l - l0] = {sx / sumrho, sy / sumrho, sz / sumrho};
-            double vol = (b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]);
-            double mass = sumrho / Nrandom * vol;
+        // (a TreeNodeBoxDensityCalculator's mass is the distribution's massInBox: no samples, no density range)
+        auto decideMass = [&](int l, double vol, double mass, double mn, double mx) {
             bool needDivision = always;
             if (!needDivision && maxMassFraction > 0 && mass / totalmass >= maxMassFraction) needDivision = true;
             if (!needDivision && maxOpticalDepth > 0 &&
@@ -254,7 +266,23 @@ void buildOctree(const Ctx& c, const XmlElement* e, const Model& model, OctreeGr
             }
             divide[l - l0] = needDivision;
         };
-        const bool onDevice = deviceSampling(
+        auto decide = [&](int l, double sumrho, double sx, double sy, double sz, double mn, double mx) {
+            const double* b = tb.box(l);
+            if (bary) bc[l - l0] = {sx / sumrho, sy / sumrho, sz / sumrho};
+            double vol = (b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]);
+            decideMass(l, vol, sumrho / Nrandom * vol, mn, mx);
+        };
+        if (massSubdivide) {
+            // TreeNodeBoxDensityCalculator: every node of the pass from massInBox, no draws
+            std::vector<double> boxes(6 * sampled.size()), mass(sampled.size());
+            for (size_t q = 0; q < sampled.size(); q++) std::memcpy(&boxes[6 * q], tb.box(sampled[q]), 6 * sizeof(double));
+            particleMasses(c, *model.particles, boxes.data(), sampled.size(), mass.data());
+            for (size_t q = 0; q < sampled.size(); q++) {
+                const double* b = &boxes[6 * q];
+                decideMass(sampled[q], (b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]), mass[q], 0, 0);
+            }
+        }
+        const bool onDevice = massSubdivide || deviceSampling(
             c, model.dust, sampled.size(), Nrandom, kDensNode,
             [&](size_t q, double* b) { std::memcpy(b, tb.box(sampled[q]), 6 * sizeof(double)); },
             [&](size_t q, const double* o) { decide(sampled[q], o[0], o[1], o[2], o[3], o[4], o[5]); });
